@@ -11,11 +11,18 @@ N > 1) + global-norm clip + AdamW.  Workload = BASELINE.json configs[2]/[3]: whi
 ("full" mode; `--mode recipe` = the README recipe with --freeze_encoder and a shared encoder).  Weights are seeded
 random (no checkpoints exist offline), data is synthetic.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel class (the bf16 MFMA GEMM): its launches are
-bracketed by HIP events on the launch stream during one extra instrumented step after the timed region.
-`cpu_baseline` times the reference path itself (the `transformers` classes under the reference's train_step,
-oracle/reference_cpu_step.py) on a bounded sample on the host cores.  With N > 1 every rank checks after the timed
-steps that its parameters are bit-identical to rank 0's (data-parallel replicas must not diverge).
+Rank 0 prints ONE JSON line.  A plain run sets up, picks the faster way to issue the step (mode_selection), warms up,
+times the K steps, writes its outputs (`--dump-outputs DIR`) and prints the line.  `--dump-outputs DIR` runs the timed
+path once more after the timed steps, from the seeded initial weights, and writes what that step computed as float32 .npy
+files (dump_outputs): inputs and starting state are seeded, so two builds run with the same arguments can be compared
+output for output.
+
+`--full` adds everything else the benchmark measures or checks, after the timed region: the in-process A/B legs (`ab`),
+`roofline` for the dominant kernel class (the bf16 MFMA GEMM: its launches bracketed by HIP events on the launch stream
+during one extra instrumented step), the reference's loop body over the drop-in modules (`via_reference_loop`),
+`cpu_baseline` (the reference path itself -- the `transformers` classes under the reference's train_step,
+oracle/reference_cpu_step.py -- on a bounded sample on the host cores) and, with N > 1, the check that every rank's
+parameters are bit-identical to rank 0's (data-parallel replicas must not diverge).
 """
 import argparse
 import json
@@ -105,8 +112,16 @@ def main():
     ap.add_argument("--dp-probe", action="store_true",
                     help="run the data-parallel mode selection (dp_mode_selection) also over gloo (with --share-device: exercises "
                          "the selection and the all-reduced decision on a one-GPU box; over nccl it runs by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the A/B legs, the roofline step, the reference-loop legs, the CPU "
+                         "baseline and (N > 1) the replica check; each can still be left out with its --no-* option")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps run the timed path once more from the seeded initial state and write what "
+                         "it computed to DIR/<name>.npy (float32; see dump_outputs)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_only:
         le0, ld0 = {"tiny.en": (4, 1), "small.en": (12, 4), "large-v3": (32, 2)}[args.model]
         print(json.dumps(cpu_baseline_leg(args.model, le0, ld0, args.mode == "recipe")), flush=True)
@@ -180,6 +195,8 @@ def main():
                              comm_watchdog_s=args.comm_timeout if world > 1 else 0.0)
     del t_sd, s_sd
     torch.cuda.empty_cache()
+    # --dump-outputs: the seeded initial state, for the one step whose outputs are written (after the timed region)
+    initial = [t.clone() for t in optimizer_state(tr)] if args.dump_outputs else None
 
     B, T = args.batch, 447
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
@@ -214,7 +231,7 @@ def main():
     # label lengths that CHANGE from step to step (an A/B leg): real batches have their own (max, sum) of label lengths, so
     # the captured plans are keyed by quantised sizes (DistillationTrainer.plan_pos_quantum / plan_row_quantum)
     fresh = []
-    for i in range(8):
+    for i in range(8 if args.full else 0):
         li = torch.randint(32, 225, (B,), generator=g, device=dev)
         lab_i = ids[:, 1:].clone()
         lab_i[torch.arange(T, device=dev)[None, :] >= li[:, None]] = -100
@@ -333,7 +350,18 @@ def main():
         dt = tmax.item()
     ms_per_step = dt / args.steps * 1e3
     log(f"{ms_per_step:.1f} ms/step")
-    if world > 1:
+    if initial is not None:
+        # The outputs of a step that follows other steps differ from run to run (Adam turns the rounding differences of
+        # reordered sums into different updates, and they compound: 0.7 % on the loss after ~50 steps of the same build),
+        # so the timed path runs once more from the seeded initial state and that step's outputs are written.
+        for t, v in zip(optimizer_state(tr), initial):
+            t.copy_(v)                # (in place: a captured graph holds these addresses)
+        del initial
+        dumped = one_step()
+        sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, tr, dumped)
+    if args.full and world > 1:
         # replicas must stay bit-identical: compare every rank's master weights with rank 0's (outside the timed region)
         P = tr.student_store.P
         ref = P.clone()
@@ -360,7 +388,7 @@ def main():
     step_tflops = value / 30.0 * fl / 1e12 / world
 
     ab = None
-    if world == 1 and not args.no_ab:
+    if args.full and world == 1 and not args.no_ab:
         try:
             ab = ab_legs(tr, eager_step, graph_step, B, dense=None if args.dense else (lambda: graph_step(None)),
                          trimmed=(lambda: graph_step(Te)) if isinstance(valid_len, list) else None,
@@ -404,7 +432,7 @@ def main():
         return None
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         try:
             roofline = roofline_leg()
         except Exception as e:         # (extra information: the timed result is reported regardless)
@@ -421,7 +449,7 @@ def main():
                           (["weight-gradient"] if tr.student.wgrad_stream is not None else []) +
                           (["communication"] if red is not None and red.active and red.stream is not None else [])}
     via_loop = None
-    if world == 1 and not args.no_reference_loop:
+    if args.full and world == 1 and not args.no_reference_loop:
         # what a maintainer gets from the two-line import change alone: the drop-in modules under the
         # reference's own loop body, optimizer and loss lines -- timed here so that the cost of staying on them is a number
         del tr
@@ -434,7 +462,7 @@ def main():
         log("reference loop over the drop-in modules: " + json.dumps(via_loop))
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline leg (subprocess, bounded to 420 s) ...")
         cpu_baseline = run_cpu_baseline(args.model, args.mode)
 
@@ -653,6 +681,30 @@ def ab_legs(tr, eager_step, graph_step, B, steps=10, warm=3, dense=None, trimmed
     tr.overlap_teacher = ov_t
     tr.set_overlap_wgrad(ov_w)
     return out
+
+
+def optimizer_state(tr):
+    """Every buffer an optimizer step of the trainer changes: the student's fp32 master weights and Adam moments, their bf16
+    shadow and packed convolution weights, the device-resident step count (with them restored, the next step repeats)."""
+    st = tr.student_store
+    return [t for t in (st.P, st.M, st.V, st.S, st.conv1_packed, st.conv2_packed, tr._adam) if t is not None]
+
+
+def dump_outputs(path, tr, losses, sample=1 << 22, seed=0):
+    """What the step just run computed, as float32 .npy files under `path` (~34 MB): the losses tensor it returned (ce, kl,
+    total, labelled rows), the global gradient norm its clip used, and the student's trainable fp32 master weights after
+    its update and their gradients from its backward at one fixed, seeded sample of `sample` positions (the whole buffers
+    are gigabytes)."""
+    import numpy as np
+    st = tr.student_store
+    idx = np.sort(np.random.default_rng(seed).integers(st.train_start, st.train_end, size=sample))
+    idx = torch.from_numpy(idx).to(st.P.device)
+    out = {"losses": losses, "grad_norm": tr.grad_norm().reshape(1),
+           "student_params_sample": st.P.index_select(0, idx), "student_grads_sample": st.G.index_select(0, idx)}
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of one step from the initial state written to {path}: {sorted(out)}")
 
 
 def _kernels_sha16():

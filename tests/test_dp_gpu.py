@@ -105,7 +105,7 @@ def test_bench_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--batch", "2", "--model", "tiny.en", "--backend", "gloo", "--share-device", "--no-roofline",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=800)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

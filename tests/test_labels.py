@@ -1,12 +1,12 @@
-"""distil_whisper_amd/labels.py against the reference's own `prepare_train_dataset` (run_distillation.py:1167-1229),
-exec'd from /root/reference with stubbed tokenizer / feature extractor when the reference tree is present (build
-container), and against known answers it produced (tests/golden/labels.json, oracle/gen_golden_labels.py)."""
+"""distil_whisper_amd/labels.py against the reference's own `prepare_train_dataset` (run_distillation.py:1167-1229):
+against its answers recorded in tests/golden/labels.json (oracle/gen_golden_labels.py) and
+tests/golden/reference_calls.json (oracle/gen_golden_reference_calls.py), and against the function itself, exec'd with
+stubbed tokenizer / feature extractor, where the reference tree is present."""
 import json
 import os
 import textwrap
 
 import numpy as np
-import pytest
 
 from distil_whisper_amd.labels import prepare_train_labels
 
@@ -27,6 +27,21 @@ def make_batch(rng, n, with_column):
         r = rng.random()
         prevs.append(None if r < 0.3 else rng.integers(0, 51000, size=int(rng.integers(1, 400))).tolist())
     return toks, (prevs if with_column else None)
+
+
+def recorded(section):
+    """The reference's answers to the calls of this module (oracle/gen_golden_reference_calls.py)."""
+    with open(os.path.join(HERE, "golden", "reference_calls.json")) as f:
+        return json.load(f)[section]
+
+
+def reference_trials():
+    """(trial, tokens, prevs, timestamp_probability, condition_on_prev_probability) of the 40 comparison trials."""
+    rng = np.random.default_rng(0)
+    for trial in range(40):
+        toks, prevs = make_batch(rng, int(rng.integers(1, 9)), with_column=trial % 2 == 0)
+        tp, cp = [(0.2, 0.2), (1.0, 1.0), (0.0, 1.0), (0.5, 0.9)][trial % 4]
+        yield trial, toks, prevs, tp, cp
 
 
 def reference_labels(toks, prevs, seed, tp, cp):
@@ -51,13 +66,12 @@ def reference_labels(toks, prevs, seed, tp, cp):
     return ns["prepare_train_dataset"](batch)["labels"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present (GPU box)")
 def test_matches_reference_function():
-    rng = np.random.default_rng(0)
-    for trial in range(40):
-        toks, prevs = make_batch(rng, int(rng.integers(1, 9)), with_column=trial % 2 == 0)
-        tp, cp = [(0.2, 0.2), (1.0, 1.0), (0.0, 1.0), (0.5, 0.9)][trial % 4]
-        want = reference_labels(toks, prevs, 100 + trial, tp, cp)
+    answers = recorded("labels_trials")
+    for trial, toks, prevs, tp, cp in reference_trials():
+        want = answers[trial]
+        if os.path.exists(REF):
+            assert reference_labels(toks, prevs, 100 + trial, tp, cp) == want, trial
         np.random.seed(100 + trial)
         got = prepare_train_labels(toks, prevs, timestamp_begin=TB, timestamp_position=TPOS, decoder_prev_token_id=PREV,
                                    timestamp_probability=tp, condition_on_prev_probability=cp, max_label_length=MAXLEN)
@@ -75,28 +89,40 @@ def test_matches_golden_known_answers():
         assert got == case["labels"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present (GPU box)")
-def test_weight_decay_grouping_matches_reference_get_parameter_names():
-    """run_distillation.py:760-778 + 1386-1391 exec'd on the drop-in module: the decay set the reference would build
-    equals the oracle's name rule and the flat store's per-range weight-decay classification."""
+def micro_student_module():
     import torch
-    import torch.nn as nn
     from distil_whisper_amd.modeling import WhisperForConditionalGeneration
     from oracle import whisper_oracle as wo
     from oracle.ref_ops import RefOps
+    cfg_t = wo.CONFIGS["micro"]
+    t_sd = wo.init_state_dict(cfg_t, 3)
+    s_sd, cfg_s = wo.student_from_teacher(t_sd, cfg_t, 2, 1)
+    return WhisperForConditionalGeneration(cfg_s, ops=RefOps("cpu", lowp=torch.float32), state_dict=s_sd)
+
+
+def reference_decay_names(model):
+    """run_distillation.py:760-778 + 1386-1391 exec'd on `model`: the names the reference puts in the decay group."""
+    import torch.nn as nn
     src = open(REF).read()
     a = src.index("def get_parameter_names(model, forbidden_layer_types, forbidden_module=None):")
     b = src.index("\n\n\n", a)
     ns = {}
     exec(src[a:b], ns)
-    cfg_t = wo.CONFIGS["micro"]
-    t_sd = wo.init_state_dict(cfg_t, 3)
-    s_sd, cfg_s = wo.student_from_teacher(t_sd, cfg_t, 2, 1)
-    model = WhisperForConditionalGeneration(cfg_s, ops=RefOps("cpu", lowp=torch.float32), state_dict=s_sd)
     decay = ns["get_parameter_names"](model, [nn.LayerNorm], forbidden_module=None)
     decay = {n for n in decay if "bias" not in n}                     # run_distillation.py:1391
     named = {n for n, _ in model.named_parameters()}                  # (tied proj_out.weight is listed once by torch)
-    ref_decay = {n for n in named if n in decay}
+    return {n for n in named if n in decay}
+
+
+def test_weight_decay_grouping_matches_reference_get_parameter_names():
+    """The decay set the reference builds on the drop-in module (recorded; re-derived where the reference tree is
+    present) equals the oracle's name rule and the flat store's per-range weight-decay classification."""
+    from oracle import whisper_oracle as wo
+    model = micro_student_module()
+    named = {n for n, _ in model.named_parameters()}
+    ref_decay = set(recorded("decay_parameter_names"))
+    if os.path.exists(REF):
+        assert reference_decay_names(model) == ref_decay
     assert ref_decay == set(wo.decay_parameter_names({n: None for n in named}))
     # the flat store: every trainable entry's range carries weight decay iff the reference puts it in the decay group
     st = model.store

@@ -1,7 +1,11 @@
 """distil_whisper_amd.student_init.student_from_teacher (the function bench.py builds its student with) against the
-reference's own `init_student_model_from_teacher` (create_student_model.py:92-216), exec'd from /root/reference on a
-micro checkpoint directory with the `transformers` model class and stub processor / generation-config classes (there
-is no tokenizer on disk); plus the known layer maps of the BASELINE configurations."""
+reference's own `init_student_model_from_teacher` (create_student_model.py:92-216) on a micro checkpoint directory: its
+answers are recorded as per-tensor digests in tests/golden/reference_calls.json (oracle/gen_golden_reference_calls.py);
+where the reference tree is present the function is also exec'd with the `transformers` model class and stub processor /
+generation-config classes (there is no tokenizer on disk); plus the known layer maps of the BASELINE configurations."""
+import hashlib
+import importlib.util
+import json
 import os
 
 import numpy as np
@@ -14,6 +18,26 @@ from oracle import gen_golden_decode as gd
 from oracle import whisper_oracle as wo
 
 REF = "/root/reference/training/create_student_model.py"
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_calls.json")
+CASES = [dict(encoder_layers=None, decoder_layers=2),
+         dict(encoder_layers=2, decoder_layers=3),
+         dict(encoder_layers=3, decoder_layers=1),
+         dict(encoder_layers=None, decoder_layers=2, decoder_layers_numbers=[1, 2]),
+         dict(encoder_layers=4, decoder_layers=2, decoder_layers_numbers=[3, 3]),
+         dict(encoder_layers=None, decoder_layers=5)]
+
+
+def digest(t):
+    """Bit-exact identity of a tensor: dtype, shape and bytes."""
+    t = t.detach().contiguous().cpu()
+    h = hashlib.sha256(f"{t.dtype} {tuple(t.shape)}".encode())
+    h.update(t.numpy().tobytes())
+    return h.hexdigest()[:32]
+
+
+def micro_teacher():
+    cfg = wo.OracleConfig(64, 1, 128, 4, 5, 300, 80, pad_token_id=0, decoder_start_token_id=1)
+    return cfg, wo.init_state_dict(cfg, 3)
 
 
 def _reference_student(teacher_dir, save_dir, **kw):
@@ -45,31 +69,32 @@ def _reference_student(teacher_dir, save_dir, **kw):
     return transformers.WhisperForConditionalGeneration.from_pretrained(save_dir).state_dict()
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present (GPU box)")
-@pytest.mark.parametrize("kw", [dict(encoder_layers=None, decoder_layers=2),
-                                dict(encoder_layers=2, decoder_layers=3),
-                                dict(encoder_layers=3, decoder_layers=1),
-                                dict(encoder_layers=None, decoder_layers=2, decoder_layers_numbers=[1, 2]),
-                                dict(encoder_layers=4, decoder_layers=2, decoder_layers_numbers=[3, 3]),
-                                dict(encoder_layers=None, decoder_layers=5)])
-def test_matches_reference_init_student_model_from_teacher(tmp_path, kw):
-    pytest.importorskip("transformers")
+def reference_student_digests(tmp_path, kw):
+    """{name: digest} of the student the reference function builds from micro_teacher() (proj_out.weight left out)."""
     from transformers import WhisperForConditionalGeneration
-    cfg = wo.OracleConfig(64, 1, 128, 4, 5, 300, 80, pad_token_id=0, decoder_start_token_id=1)
-    t_sd = wo.init_state_dict(cfg, 3)
+    cfg, t_sd = micro_teacher()
     hf = WhisperForConditionalGeneration(gd.hf_config(cfg))
     full = dict(t_sd)
     full["proj_out.weight"] = t_sd["model.decoder.embed_tokens.weight"]
     hf.load_state_dict(full, strict=False)
     hf.save_pretrained(str(tmp_path / "teacher"))
     want = _reference_student(str(tmp_path / "teacher"), str(tmp_path / "student"), **kw)
+    return {k: digest(v) for k, v in want.items() if k != "proj_out.weight"}
+
+
+@pytest.mark.parametrize("kw", CASES)
+def test_matches_reference_init_student_model_from_teacher(tmp_path, kw):
+    with open(GOLD) as f:
+        want = next(c["digests"] for c in json.load(f)["student_init"] if c["kw"] == kw)
+    if os.path.exists(REF) and importlib.util.find_spec("transformers") is not None:
+        assert reference_student_digests(tmp_path, kw) == want
+    cfg, t_sd = micro_teacher()
     got, sdims = si.student_from_teacher(t_sd, WhisperDims.from_any(cfg), kw["encoder_layers"], kw["decoder_layers"],
                                          kw.get("decoder_layers_numbers"))
     assert sdims.enc_layers == (kw["encoder_layers"] or 4) and sdims.dec_layers == kw["decoder_layers"]
-    want = {k: v for k, v in want.items() if k != "proj_out.weight"}
     assert sorted(got) == sorted(want)
     for k in want:
-        assert torch.equal(got[k], want[k]), k
+        assert digest(got[k]) == want[k], k
 
 
 def test_layer_maps_of_the_baseline_configs_and_errors():

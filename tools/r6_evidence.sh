@@ -10,7 +10,7 @@ timeout 120 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_w -o b -- python
 python tools/pmc_traffic.py $O/pmc_f/b_results.db $O/pmc_w/b_results.db $O/pmc_traffic.json > $O/pmc_traffic.log 2>&1
 rm -rf $O/pmc_f $O/pmc_w
 for f in pmc_traffic.json vendor_gemm_ceiling.json attn_vendor_ceiling.json; do [ -s $O/$f ] && cp $O/$f profiles/$f; done
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err      # the driver's command
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_full.json 2> $O/bench_full.err      # the driver's command with the full report
 timeout 240 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-reference-loop --no-overlap --graph off --no-ab > $O/bench_prof.log 2>&1
 python tools/rocprof_summary.py $O/prof/bench_results.db $O/bench_kernel_stats.md > /dev/null 2>&1
 rm -rf $O/prof
@@ -31,10 +31,10 @@ sys.stdout.write(subprocess.run([sys.executable, "tools/gemm_pmc.py"] + args, ca
 PY
 rm -rf $O/g1_* $O/g2_*
 # other configs / modes
-timeout 600 python bench.py --model small.en --no-cpu-baseline --no-reference-loop > $O/bench_small_en.json 2> $O/bench_small_en.err
+timeout 600 python bench.py --model small.en --no-cpu-baseline --no-reference-loop --full > $O/bench_small_en.json 2> $O/bench_small_en.err
 MODEL=small.en timeout 300 python tools/step_breakdown.py > $O/small_en_step_breakdown.md 2> $O/small_en_step_breakdown.err
-timeout 600 python bench.py --mode recipe --no-cpu-baseline > $O/bench_recipe.json 2> $O/bench_recipe.err
-timeout 300 python bench.py --model tiny.en --batch 2 --no-cpu-baseline --no-reference-loop > $O/bench_tiny_en_b2.json 2> $O/bench_tiny.err
+timeout 600 python bench.py --mode recipe --no-cpu-baseline --full > $O/bench_recipe.json 2> $O/bench_recipe.err
+timeout 300 python bench.py --model tiny.en --batch 2 --no-cpu-baseline --no-reference-loop --full > $O/bench_tiny_en_b2.json 2> $O/bench_tiny.err
 timeout 300 python tools/bench_longform.py > $O/longform_bench.json 2> $O/longform.err
 timeout 300 python tools/gemm_m128_probe.py > $O/gemm_small_m_probe.txt 2>&1
 timeout 300 python tools/bench_pseudo_label.py > $O/pseudo_label_bench.json 2> $O/pseudo_label.err
