@@ -29,13 +29,11 @@ struct GemmP {
     bf16* kv_out;          // output columns >= kv_split of row m go to the K/V cache instead of C:
     long kv_ld;            //   kv_out[((m / kv_rpb) * kv_pitch + kv_row0 + m % kv_rpb) * kv_ld + (n - kv_split)]
     int kv_split, kv_rpb, kv_pitch, kv_row0;
-    int stage_next;        // debug key 11; bit 4 (16): the software-pipelined kernels skip the epilogue (profiling: tools/gemm_overhead.py)
+    int stage_next;        // bit 7 (128): request the next tile's first operand tile before the epilogue (gemm_wp.h); bit 4 (16): the
+                           // 16x16x32 kernels skip the epilogue (profiling; gemm_wp16.h); debug key 11
     int zg_f16;            // z_out / zgrad hold gelu'(z) in fp16 instead of z in bf16 (see DwGemm.z_is_gelu_grad)
     int* sched;            // persistent kernels: 9 device counters of this stream (dynamic job hand-out), or null
-    int stagger;           // debug key 12: start offsets of the persistent workgroups (gemm_wp.h), 0 = none
     float* colsum;         // f32 [n] += column sums of the stored C (DwGemm.colsum_out), or null
-    long long* trace;      // debug keys 13 / 14 (low / high half of a device pointer): per-workgroup phase timestamps of
-                           // the first 8 tiles (gemm_wp.h DW_TRACE; tools/gemm_phase_trace.py), null = off
 };
 
 // Persistent workgroups: the grid holds at most one workgroup per CU; each walks a list of output-tile jobs.
@@ -204,22 +202,15 @@ __device__ __forceinline__ int gemm_epi_flavour(const GemmP& p) {
 }
 // Stores of the 2-byte outputs (C in bf16, z_out) carry the non-temporal hint.  An output of hundreds of MB written through L2 /
 // the Infinity Cache the default way evicts the operand panels the other workgroups are still reading: sustained, the fc1 shape
-// (N = 5120) gains 4-13 %, fc2 1 %, qkv loses 1 % (tools/gemm_w4_probe.py); the whole step -1.35 % in one process against a
-// build with -DDW_EPI_NT=0 (tools/ab_step.py, tools/build_variant_lib.sh).  fp32 outputs (the residual stream, the weight-gradient
+// (N = 5120) gains 4-13 %, fc2 1 %, qkv loses 1 %; the whole step -1.35 % in one process against a build with plain
+// stores (DESIGN_HISTORY.md).  fp32 outputs (the residual stream, the weight-gradient
 // slabs) are read again by the next kernel and keep the default policy (NT there: +0.3 %); so do LayerNorm's and the attention
 // kernels' outputs (NT: +0.5 % / +2.9 % -- their consumers run right behind them).
 // Compile time on purpose: with a per-launch flag both store forms sit in every walk and the larger image costs more than the
 // hint returns (and `if (nt) __builtin_nontemporal_store(..) else *p = v` is merged into ONE plain store: the hint is metadata).
-#ifndef DW_EPI_NT
-#define DW_EPI_NT 1
-#endif
 template <class T>
 __device__ __forceinline__ void gemm_store_out(T* dst, const T& v) {
-#if DW_EPI_NT
     __builtin_nontemporal_store(v, dst);
-#else
-    *dst = v;
-#endif
 }
 template <int F = -1>
 __device__ __forceinline__ void gemm_epi_vec4(const GemmP& p, float (&v)[4], const f32x4& b4, bool plain, bool have_side,
@@ -346,23 +337,18 @@ __device__ __forceinline__ void gemm_lds_barrier() {
 template <int FM, int FN, int TN, int PFDIST = 0, class Hook = GemmNoHook, bool SWZ = false, int LAY = 32, int JOFF = 0, class Acc = f32x16[FM][FN]>
 __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* smem, int wave, int lane,
                                               int m0_, int wm0_, int n0_, int wn0_, int ks_, Hook hook = Hook(),
-                                              const float* lds_bias = nullptr, long long* tslot = nullptr) {
-    // tslot (phase trace, tools/gemm_phase_trace.py; thread 0 only, or null): [5] behind the leading barrier, [6] first slab
-    // transposed and its stores issued
+                                              const float* lds_bias = nullptr) {
     // lds_bias: the tile's bias slice (BN floats from column n0) staged in LDS by the caller at the start of the tile
     // (interior tiles only).  A bias read from global memory here is an ordinary load whose vmcnt wait also drains every
     // operand DMA the caller has in flight for the NEXT tile (the counter retires in order).
     static_assert(!SWZ || TN == 64, "swizzled patch: 16 slots of 16 bytes per row");
-#ifndef DW_EPI_LAUNDER
-#define DW_EPI_LAUNDER 1
-#endif
     // Every lane-dependent value of the walks below (patch addresses under their swizzle, lane offsets of C / z / residual)
     // is a function of `lane` alone, i.e. invariant over the persistent workgroup's tile loop: hoisted in front of it they are
     // live across the K loop, where every register is taken, and get SPILLED -- and a scratch reload inside a walk is a VMEM
     // load whose vmcnt(0) wait also waits for the acknowledgement of the global store issued just before it (the fp32-residual
     // walk of the 320-row kernel did that once per row group: 100 B of scratch, 163 scratch instructions).  An opaque
     // redefinition of `lane` per tile keeps the few instructions that derive them inside the epilogue.
-    if constexpr (DW_EPI_LAUNDER != 0) asm volatile("" : "+v"(lane));
+    asm volatile("" : "+v"(lane));
     // tile and wave coordinates are the same in every lane: say so (the job index comes out of an LDS slot, which the
     // compiler must otherwise treat as a per-lane value, and every row address would be 64-bit vector arithmetic)
     const int m0 = __builtin_amdgcn_readfirstlane(m0_), wm0 = __builtin_amdgcn_readfirstlane(wm0_);
@@ -426,7 +412,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
         // (the FN * 4 write addresses are re-derived per slab from an opaque copy of the lane index: held across the slabs, two
         // of them were spilled and reloaded behind a vmcnt(0) that waited for the previous slab's stores)
         int l2 = lane;
-        if constexpr (DW_EPI_LAUNDER != 0) asm volatile("" : "+v"(l2));
+        asm volatile("" : "+v"(l2));
         const int lrow2 = LAY == 32 ? (l2 & 31) : (l2 & 15), lcol2 = LAY == 32 ? (l2 >> 5) * 4 : (l2 >> 4) * 4;
         static_for<0, FN * 4>([&](auto qc) __attribute__((always_inline)) {
             constexpr int q = decltype(qc)::value;
@@ -481,20 +467,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
                 constexpr int gi = decltype(gc)::value;
                 constexpr int slot = gi % PFD;
                 constexpr long rg = (gi / NIT) * 32 + (gi % NIT) * RPI;              // first row of the row group in the wave tile
-#ifndef DW_EPI_NT_SIDE
-#define DW_EPI_NT_SIDE 1       // 1 (default since round 6): gelu'(z) -- 491 MB per dX-of-fc2 launch, read once -- is loaded with the non-temporal hint:
-                               // 338.7 -> 337.2 ms per step against a variant build in one process (tools/ab_keys.py `lib`); 2: the residual, 3: both (3 = 1 within noise)
-#endif
-                if (want_z) {
-                    if constexpr ((DW_EPI_NT_SIDE & 1) != 0) zq[slot] = __builtin_nontemporal_load((const bf16x4*)(zg_u + rg * p.ldzg * 2 + l_zg));
-                    else zq[slot] = *(const bf16x4*)(zg_u + rg * p.ldzg * 2 + l_zg);
-                }
+                // gelu'(z) -- 491 MB per dX-of-fc2 launch, read once -- is loaded with the non-temporal hint: 338.7 -> 337.2 ms per
+                // step against a build with plain loads in one process (round 6); the hint on the residual as well was within noise
+                if (want_z) zq[slot] = __builtin_nontemporal_load((const bf16x4*)(zg_u + rg * p.ldzg * 2 + l_zg));
                 if (want_r) {
                     const char* src = r_u + rg * p.ldr * esr + l_r;
-                    if (r_f32) {
-                        if constexpr ((DW_EPI_NT_SIDE & 2) != 0) rq[slot] = __builtin_nontemporal_load((const f32x4*)src);
-                        else rq[slot] = *(const f32x4*)src;
-                    }
+                    if (r_f32) rq[slot] = *(const f32x4*)src;
                     else {
                         const f32x2 t = *(const f32x2*)src;
                         rq[slot][0] = t[0]; rq[slot][1] = t[1];
@@ -504,22 +482,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
             if constexpr (side) static_for<0, PFD>([&](auto gc) __attribute__((always_inline)) { side_load(gc); });
             hook();
             if constexpr (SWZ) gemm_lds_barrier(); else __syncthreads();   // every wave is done reading the operand tiles
-            if (tslot) tslot[5] = (long long)__builtin_amdgcn_s_memrealtime();
             static_for<0, FM>([&](auto ic) __attribute__((always_inline)) {
                 constexpr int i = decltype(ic)::value;
-                if (i == 1 && tslot) tslot[6] = (long long)__builtin_amdgcn_s_memrealtime();
                 to_patch(ic);
-#ifndef DW_EPI_READS_FIRST
-#define DW_EPI_READS_FIRST 1
-#endif
-#ifndef DW_EPI_RG5
-#define DW_EPI_RG5 2
-#endif
                 // (8-wave kernels: all row groups of the slab are read back from the patch first -- the slab's 32 accumulator
                 // registers have just died -- instead of one read -> lgkmcnt(0) -> arithmetic -> store round per row group with
                 // the LDS latency exposed every time)
-                constexpr bool RF = SWZ && DW_EPI_READS_FIRST != 0;
-                constexpr int RG = FM == 5 ? DW_EPI_RG5 : NIT;     // (the 320-row kernel has no 32 free registers: a part of a slab at a time)
+                constexpr bool RF = SWZ;
+                constexpr int RG = FM == 5 ? 2 : NIT;     // (the 320-row kernel has no 32 free registers: a part of a slab at a time)
                 f32x4 a4s[RF ? RG : 1];
                 static_for<0, NIT>([&](auto itc) __attribute__((always_inline)) {
                     constexpr int it = decltype(itc)::value;
@@ -573,7 +543,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
             lds_cfloat_t* const bsrc = (lds_cfloat_t*)lds_bias + wn0 + lcol;
             hook();
             gemm_lds_barrier();                       // every wave is done reading the operand tiles
-            if (tslot) tslot[5] = (long long)__builtin_amdgcn_s_memrealtime();
             const int rr = lane >> 3, sc = lane & 7;  // row-major side: 8 rows per instruction, 8 lanes x 16 B per row
             char* const wr = bp + lrow * PRS + lcol * 2;      // transposing side: + qrow(q) * PRS + qcol(q) * 2
             const char* const rd = bp + rr * PRS + sc * 16;   // row-major side:   + it * 8 * PRS (+ 8)
@@ -592,15 +561,11 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
                 static_for<0, 4>([&](auto itc) __attribute__((always_inline)) {
                     constexpr int it = decltype(itc)::value;
                     constexpr long rg = i * 32 + it * 8;
-#ifdef DW_EPI_ABLATE      // (profiling builds: key 11 bit 32 = the accumulator-side walk without its global stores)
-                    if (!(p.stage_next & 32) || o4[it][0] == 0x12345678u)
-#endif
                     gemm_store_out((u32x4*)(dst_u + rg * ld * 2 + l16), o4[it]);
                 });
             };
             static_for<0, FM>([&](auto ic) __attribute__((always_inline)) {
                 constexpr int i = decltype(ic)::value;
-                if (i == 1 && tslot) tslot[6] = (long long)__builtin_amdgcn_s_memrealtime();
                 f16x4 gq[HAS_G ? FN * 4 : 1];
                 // (quads in groups of four: their four bias reads are in flight together -- one LDS latency per group, not per quad)
                 static_for<0, FN>([&](auto gc) __attribute__((always_inline)) {
@@ -653,11 +618,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
                 }
             });
         };
-#ifndef DW_EPI16
-#define DW_EPI16 1
-#endif
         // 16-byte accesses of C (and z_out): pointer and leading dimension multiples of 8 elements
-        const bool ok16 = DW_EPI16 && SWZ && p.c_dtype != DW_F32 && ((uintptr_t)p.c & 15) == 0 && (p.ldc & 7) == 0 && (!p.bias || lds_bias) &&
+        const bool ok16 = SWZ && p.c_dtype != DW_F32 && ((uintptr_t)p.c & 15) == 0 && (p.ldc & 7) == 0 && (!p.bias || lds_bias) &&
                           (!p.z_out || (((uintptr_t)p.z_out & 15) == 0 && (p.ldz & 7) == 0));
 #define DW_EPI_CASE16(F)                                                                             \
     case (F):                                                                                        \

@@ -5,7 +5,7 @@
 #pragma once
 #include "gemm_common.h"
 
-template <int BM, int BN, int WM, int WN, bool TA, bool TB, int VAR>
+template <int BM, int BN, int WM, int WN, bool TA, bool TB>
 __global__ __launch_bounds__(64 * WM * WN, (BM == 128 ? 2 : 1) * WM * WN / 4) void gemm_kernel(const GemmP p) {
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM, TN = BN / WN;
@@ -124,66 +124,25 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 ? 2 : 1) * WM * WN / 4) vo
     auto compute = [&](int buf) {
         const char* tA = smem + buf * STAGE;
         const char* tB = tA + BM * 128;
-        if (VAR == 0) {
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                bf16x8 af[FM], bfr[FN];
+        for (int kk = 0; kk < 4; ++kk) {
+            bf16x8 af[FM], bfr[FN];
 #pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    if (TA) af[i] = frag_kmajor<BM>(tA, wm0 + i * 32, kk, lane);
-                    else af[i] = frag_rows(tA, (wm0 >> 5) + i, kk, lane);
-                }
-#pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    if (TB) bfr[j] = frag_kmajor<BN>(tB, wn0 + j * 32, kk, lane);
-                    else bfr[j] = frag_rows(tB, (wn0 >> 5) + j, kk, lane);
-                }
-                static_for<0, FM>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    static_for<0, FN>([&](auto jc) {
-                        constexpr int j = decltype(jc)::value;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-                    });
-                });
+            for (int i = 0; i < FM; ++i) {
+                if (TA) af[i] = frag_kmajor<BM>(tA, wm0 + i * 32, kk, lane);
+                else af[i] = frag_rows(tA, (wm0 >> 5) + i, kk, lane);
             }
-        } else {
-            // explicit register double buffer: the fragments of sub-step kk+1 are requested from LDS before the
-            // MFMA cluster of sub-step kk is issued, so the LDS latency hides behind FM*FN matrix instructions
-            bf16x8 af[2][FM], bfr[2][FN];
-            auto load = [&](auto kc, auto sc) {
-                constexpr int kk = decltype(kc)::value;
-                constexpr int sl = decltype(sc)::value;
 #pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    if (TA) af[sl][i] = frag_kmajor<BM>(tA, wm0 + i * 32, kk, lane);
-                    else af[sl][i] = frag_rows(tA, (wm0 >> 5) + i, kk, lane);
-                }
-#pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    if (TB) bfr[sl][j] = frag_kmajor<BN>(tB, wn0 + j * 32, kk, lane);
-                    else bfr[sl][j] = frag_rows(tB, (wn0 >> 5) + j, kk, lane);
-                }
-            };
-            load(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-            static_for<0, 4>([&](auto kc) {
-                constexpr int kk = decltype(kc)::value;
-                constexpr int cur = kk & 1;
-                if constexpr (kk < 3) load(std::integral_constant<int, kk + 1>{}, std::integral_constant<int, cur ^ 1>{});
-                static_for<0, FM>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    static_for<0, FN>([&](auto jc) {
-                        constexpr int j = decltype(jc)::value;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[cur][j], af[cur][i], acc[i][j], 0, 0, 0);
-                    });
+            for (int j = 0; j < FN; ++j) {
+                if (TB) bfr[j] = frag_kmajor<BN>(tB, wn0 + j * 32, kk, lane);
+                else bfr[j] = frag_rows(tB, (wn0 >> 5) + j, kk, lane);
+            }
+            static_for<0, FM>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                static_for<0, FN>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value;
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
                 });
-                if (VAR == 1) {
-                    // pin the interleave: LDS reads between consecutive MFMAs (DS_READ mask 0x100, MFMA 0x8)
-#pragma unroll
-                    for (int q = 0; q < FM * FN; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, (TA || TB) ? 2 : 1, 0);
-                    }
-                }
             });
         }
     };
@@ -207,11 +166,10 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 ? 2 : 1) * WM * WN / 4) vo
   gemm_jobs_end(p, jobs);
 }
 
-// launch knobs owned by gemm.hip (dw_debug_set)
-extern int g_gemm_persistent;
+// launch knob owned by gemm.hip (dw_debug_set key 1)
 extern int g_gemm_strip;
 
-template <int BM, int BN, int WM, int WN, int VAR>
+template <int BM, int BN, int WM, int WN>
 static int launch_tile(const GemmP& p0, int ta, int tb, hipStream_t s) {
     GemmP p = p0;
     const int tiles_m = (p.m + BM - 1) / BM;
@@ -220,12 +178,12 @@ static int launch_tile(const GemmP& p0, int ta, int tb, hipStream_t s) {
     p.strip = gemm_strip_width(p.k, p.tiles_n, g_gemm_strip);
     // persistent launch for the 256-tile (one workgroup per CU, 256 CUs): only when there are more jobs than CUs
     int nblk = p.nwg * p.split_k;
-    if (BM == 256 && nblk > g_gemm_cus && g_gemm_persistent) nblk = g_gemm_cus;
+    if (BM == 256 && nblk > g_gemm_cus) nblk = g_gemm_cus;
     dim3 grid(nblk), block(64 * WM * WN);
-    if (!ta && !tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, false, false, VAR>), grid, block, 0, s, p);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, false, true, VAR>), grid, block, 0, s, p);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, true, false, VAR>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, true, true, VAR>), grid, block, 0, s, p);
+    if (!ta && !tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, false, false>), grid, block, 0, s, p);
+    else if (!ta && tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, false, true>), grid, block, 0, s, p);
+    else if (ta && !tb) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, true, false>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, true, true>), grid, block, 0, s, p);
     DW_CHECK_LAUNCH();
     return DW_OK;
 }

@@ -2,5 +2,5 @@
 #include "gemm_kernel.h"
 
 int dw_gemm_tile128_launch(const GemmP& p, int ta, int tb, hipStream_t s) {
-    return launch_tile<128, 128, 2, 4, 0>(p, ta, tb, s);
+    return launch_tile<128, 128, 2, 4>(p, ta, tb, s);
 }

@@ -2,5 +2,5 @@
 #include "gemm_kernel.h"
 
 int dw_gemm_tile256_launch(const GemmP& p, int ta, int tb, hipStream_t s) {
-    return launch_tile<256, 256, 4, 4, 0>(p, ta, tb, s);
+    return launch_tile<256, 256, 4, 4>(p, ta, tb, s);
 }

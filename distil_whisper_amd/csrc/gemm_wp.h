@@ -79,31 +79,18 @@ __device__ __forceinline__ void wp_dma16u(const i32x4_t& rsrc, unsigned lds_addr
 // ... with the piece's compile-time offset added on the way into M0 (one scalar instruction instead of two)
 // ... and, for the kernels whose pieces differ by a scalar stride (UNI), the piece's scalar offset computed in the wait state the
 // M0 write needs anyway (instead of an s_nop and a separate s_add)
-// (-DDW_DMA_NT=1 / 2 / 3: the loads of the A / B / both operands carry the non-temporal hint -- experiments, see gemm_store_out)
-#ifndef DW_DMA_NT
-#define DW_DMA_NT 0
-#endif
-template <int IMM, bool ISA = true>
+template <int IMM>
 __device__ __forceinline__ void wp_dma16p(const i32x4_t& rsrc, unsigned lds_base, unsigned voffset, int kbase, int piece_off) {
     int so;
-    if constexpr ((DW_DMA_NT & (ISA ? 1 : 2)) != 0)
-        asm volatile("s_add_u32 m0, %1, %5\n\ts_add_u32 %0, %4, %6\n\tbuffer_load_dwordx4 %2, %3, %0 offen nt lds"
-                     : "=&s"(so) : "s"(lds_base), "v"(voffset), "s"(rsrc), "s"(kbase), "i"(IMM), "s"(piece_off) : "scc");
-    else
-        asm volatile("s_add_u32 m0, %1, %5\n\ts_add_u32 %0, %4, %6\n\tbuffer_load_dwordx4 %2, %3, %0 offen lds"
-                     : "=&s"(so) : "s"(lds_base), "v"(voffset), "s"(rsrc), "s"(kbase), "i"(IMM), "s"(piece_off) : "scc");
+    asm volatile("s_add_u32 m0, %1, %5\n\ts_add_u32 %0, %4, %6\n\tbuffer_load_dwordx4 %2, %3, %0 offen lds"
+                 : "=&s"(so) : "s"(lds_base), "v"(voffset), "s"(rsrc), "s"(kbase), "i"(IMM), "s"(piece_off) : "scc");
 }
-template <int IMM, bool ISA = true>
+template <int IMM>
 __device__ __forceinline__ void wp_dma16i(const i32x4_t& rsrc, unsigned lds_base, unsigned voffset, int soffset) {
-    if constexpr ((DW_DMA_NT & (ISA ? 1 : 2)) != 0)
-        asm volatile("s_add_u32 m0, %0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds"
-                     :: "s"(lds_base), "v"(voffset), "s"(rsrc), "s"(soffset), "i"(IMM) : "scc");
-    else
-        asm volatile("s_add_u32 m0, %0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                     :: "s"(lds_base), "v"(voffset), "s"(rsrc), "s"(soffset), "i"(IMM) : "scc");
+    asm volatile("s_add_u32 m0, %0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                 :: "s"(lds_base), "v"(voffset), "s"(rsrc), "s"(soffset), "i"(IMM) : "scc");
 }
 
-// ASMDMA = false builds the same kernel with the operand DMA issued through the compiler builtin (A/B reference only).
 // BM = 320 (row-major A only): a 320 x 256 block tile, 160 x 64 per wave (5 x 2 accumulators).  M = 48000 is 150 row
 // tiles exactly and N = 1280 / 2560 / 3840 give 750 / 1500 / 2250 tiles = 2.93 / 5.86 / 8.79 rounds of the 256 CUs
 // where 256-row tiles give 940 / 1880 / 2820 = 3.67 / 7.34 / 11.02 (the last round a third full); per MFMA the wave
@@ -114,19 +101,19 @@ __device__ __forceinline__ void wp_dma16i(const i32x4_t& rsrc, unsigned lds_base
 // boundary (measured: 1.1 us per K tile, the same as the lock-step 128 x 128 kernel).  With three stages the pieces of K tile
 // t + 2 are requested during tile t and the boundary waits with a COUNTED vmcnt (the newest NH0 + NH1 loads may stay in flight:
 // the counter retires in order), one barrier per K tile as before.
-template <bool TA, bool TB, int WM, int WN, bool ASMDMA = true, int DBG = 0, int BM = 256, int NST = 2>
+// ASMDMA / DBG: always true / 0 (launch_wp).  They keep the kernel's symbol -- gemm_wp_kernel<.., true, 0, BM, NST> -- that the
+// committed profiles, the traffic classes of tools/pmc_traffic.py and the scratch budgets of tests/test_codegen.py name.
+template <bool TA, bool TB, int WM, int WN, bool ASMDMA, int DBG, int BM, int NST>
 __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(const GemmP p) {
+    static_assert(ASMDMA && DBG == 0, "one build of the loop: inline-assembly operand DMA, no ablation");
     constexpr int BN = 256, NW = WM * WN, FM = BM / WM / 32, FN = BN / WN / 32, TN = BN / WN;
-    static_assert(NST == 2 || (NST == 3 && DBG == 0 && ASMDMA && BM < 256), "three stages: the 128-row tile");
+    static_assert(NST == 2 || (NST == 3 && BM < 256), "three stages: the 128-row tile");
     static_assert(NW * 32 * (TN + 4) * 4 <= 2 * (BM + BN) * 128, "epilogue patches must fit the operand buffers");
     static_assert(BM == 256 || !TA, "the k-major A image is built for 256-row tiles");
     constexpr int CPA = BM / 8 / NW, CPB = BN / 8 / NW;   // DMA pieces (1 KiB) per wave per operand per K tile
     constexpr int CP = CPB;
     constexpr bool UNI = BM == 320;                     // (BM = 128 keeps one clamped offset per piece like BM = 256: any M)
-#ifndef DW_EPF
-#define DW_EPF 4
-#endif
-    constexpr int EPF = DW_EPF;                       // epilogue side-input prefetch distance of the 320-row tile (register budget)
+    constexpr int EPF = 4;                            // epilogue side-input prefetch distance of the 320-row tile (register budget)
     static_assert(CPA * 8 * NW == BM && CPB * 8 * NW == BN && CPA <= 8 && CPB <= 8, "piece split");
     // a K tile is requested in two halves; half h carries A pieces [HA0(h), HA0(h+1)) and B pieces [HB0(h), HB0(h+1))
     constexpr int NA0 = (CPA + 1) / 2, NB0 = CPB / 2;          // pieces of half 0
@@ -144,20 +131,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
     __shared__ int job_slot[2];
     GemmJobs jobs;
     gemm_jobs_begin(p, jobs, job_slot);
-    if (p.stagger > 0) {
-        // Experiment (dw_debug_set key 12 = S | unit << 8): the workgroups of a launch run their tiles in lockstep, so every
-        // tile round ends with 256 CUs storing at once (33 MB in ~6 us = the HBM write rate) while the matrix pipes idle.
-        // Start offsets (local index mod S) x unit x ~4 us spread the bursts; the dynamic job hand-out shares the tiles.
-        const int k = ((blockIdx.x >> 3) % (p.stagger & 255)) * (p.stagger >> 8);
-        for (int i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-    // phase timestamps (100 MHz constant clock) of the first 8 tiles of every workgroup: 0 tile start, 1 first operand tile
-    // landed, 2 K loop done, 3 epilogue returned (wave 0: its stores are issued), 4 behind the tile's last barrier
-#define DW_TRACE(slot)                                                                                             \
-    do {                                                                                                           \
-        if (p.trace && tid == 0 && jobs.iter < 8)                                                                  \
-            p.trace[((long)blockIdx.x * 8 + jobs.iter) * 8 + (slot)] = (long long)__builtin_amdgcn_s_memrealtime(); \
-    } while (0)
     bool prefetched = false;     // this tile's first operand tile was requested before the previous tile's epilogue
     while (jobs.cur < jobs.cnt) {
         // The K loop's per-lane addresses (operand-load offsets, fragment addresses) are functions of the lane index alone; derived
@@ -166,7 +139,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
         // for the previous slab's global stores, ~1 us per slab).
         int lane_k = lane;
         asm volatile("" : "+v"(lane_k));
-        DW_TRACE(0);
         gemm_jobs_prefetch(p, jobs, job_slot);
         int tm, tn, ks;
         gemm_job_decode(p, jobs.start + jobs.cur, tm, tn, ks);
@@ -260,24 +232,13 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
             constexpr int idx = j < 2 * nmin ? j / 2 : j - nmin;             // index within the operand's share of the half
             constexpr int i = (isA ? (h ? NA0 : 0) : (h ? NB0 : 0)) + idx;
             static_assert(j < na + nb, "load index");
-            const char* tA = smem + ((DBG & 2) ? (buf & 1) : buf) * STAGE + wave * 1024 + i * (NW * 1024);
-            if constexpr ((DBG & 2) != 0) { if (buf < 8) return; }                  // ablation: no operand DMA in the loop
-            if constexpr (ASMDMA) {
-                const unsigned lb = smem_w + (unsigned)(((DBG & 2) ? (buf & 1) : buf) * STAGE);
-                if constexpr (UNI) {
-                    if constexpr (isA) wp_dma16p<i * (NW * 1024)>(ra, lb, offA[0], kA, i * pieceA);
-                    else wp_dma16p<i * (NW * 1024) + BM * 128, false>(rb, lb, offB[0], kB, i * pieceB);
-                } else {
-                    if constexpr (isA) wp_dma16i<i * (NW * 1024)>(ra, lb, offA[i], kA);
-                    else wp_dma16i<i * (NW * 1024) + BM * 128, false>(rb, lb, offB[i], kB);
-                }
+            const unsigned lb = smem_w + (unsigned)(buf * STAGE);
+            if constexpr (UNI) {
+                if constexpr (isA) wp_dma16p<i * (NW * 1024)>(ra, lb, offA[0], kA, i * pieceA);
+                else wp_dma16p<i * (NW * 1024) + BM * 128>(rb, lb, offB[0], kB, i * pieceB);
             } else {
-                const auto bA = __builtin_amdgcn_make_buffer_rsrc((void*)gA, 0, 0x7fffffff, 0x00020000);
-                const auto bB = __builtin_amdgcn_make_buffer_rsrc((void*)gB, 0, 0x7fffffff, 0x00020000);
-                if constexpr (isA)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(bA, (lds_void_t*)tA, 16, offA[i], kA, 0, 0);
-                else
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(bB, (lds_void_t*)(tA + BM * 128), 16, offB[i], kB, 0, 0);
+                if constexpr (isA) wp_dma16i<i * (NW * 1024)>(ra, lb, offA[i], kA);
+                else wp_dma16i<i * (NW * 1024) + BM * 128>(rb, lb, offB[i], kB);
             }
         };
         auto dma1 = [&](auto hc, auto jc, int buf) __attribute__((always_inline)) { dma1x(rsA, rsB, hc, jc, buf); };
@@ -287,8 +248,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
         bf16x8 af[2][FM], bfr[2][FN];
         auto frags = [&](auto sc, auto kc, int buf) {
             constexpr int set = decltype(sc)::value, kk = decltype(kc)::value;
-            if constexpr ((DBG & 1) != 0) { if (buf < 8) return; }                  // ablation: no fragment reads in the loop
-            const char* tA = smem + ((DBG & 1) ? (buf & 1) : buf) * STAGE;
+            const char* tA = smem + buf * STAGE;
             const char* tB = tA + BM * 128;
 #pragma unroll
             for (int i = 0; i < FM; ++i) {
@@ -342,8 +302,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
         using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>;
         using I3 = std::integral_constant<int, 3>;
-        using I8 = std::integral_constant<int, 8>;
-        (void)sizeof(I8);
 
         // ---- prologue: tile 0 whole, first half of tile 1, fragments of (0, 0) ----
         const bool tile_in = m0 + BM <= p.m && n0 + BN <= p.n;
@@ -359,7 +317,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
             else if (nt > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NH0 + NH1) : "memory");
             else wait_vm0();
             __syncthreads();
-            DW_TRACE(1);
             frags(I0{}, I0{}, 0);
             __builtin_amdgcn_sched_barrier(0);
             // one K tile out of buffer b0; b1 / b2: the buffers of tiles t+1 / t+2.  M1..M3: tile t+1 / t+2 / t+3 exists.
@@ -397,9 +354,9 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
             if (nt >= 2) { body3(std::true_type{}, std::false_type{}, std::false_type{}, b0, b1, b2); rot(); }
             body3(std::false_type{}, std::false_type{}, std::false_type{}, b0, b1, b2);
         } else {
-        if (!prefetched) { dma(I0{}, (DBG & 2) ? 8 : 0); dma(I1{}, (DBG & 2) ? 8 : 0); }
+        if (!prefetched) { dma(I0{}, 0); dma(I1{}, 0); }
         kA += stepA; kB += stepB;
-        if (nt > 1) dma(I0{}, (DBG & 2) ? 9 : 1);
+        if (nt > 1) dma(I0{}, 1);
         if (nt > 1) {      // tile 0 has landed when only the NH0 loads of tile 1's first half are outstanding
             if constexpr (NH0 == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else if constexpr (NH0 == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
@@ -407,9 +364,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
             else { static_assert(NH0 == 4 || NH0 == 8 || NH0 == 5 || NH0 == 3, "vmcnt immediate"); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
         } else wait_vm0();
         __syncthreads();
-        DW_TRACE(1);
-        frags(I0{}, I0{}, (DBG & 1) ? 8 : 0);
-        if constexpr ((DBG & 1) != 0) frags(I1{}, I1{}, 8);
+        frags(I0{}, I0{}, 0);
         __builtin_amdgcn_sched_barrier(0);
 
         // one K tile; MORE1: tile t+1 exists, MORE2: tile t+2 exists.  (kA, kB) point at tile t+1 on entry.
@@ -419,7 +374,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
             // sub-step 0: second half of tile t+1
             PIN_SET(0);
             frags(I1{}, I1{}, buf);
-            if constexpr (MORE1) { substep(I0{}, I1{}, I2{}, buf ^ 1); if constexpr ((DBG & 4) == 0) { kA += stepA; kB += stepB; } }   // (DBG & 4: every DMA of the loop re-fetches the first K tiles -- always L2-warm; tools/gemm_dma_diag.py)
+            if constexpr (MORE1) { substep(I0{}, I1{}, I2{}, buf ^ 1); kA += stepA; kB += stepB; }
             else substep(I0{}, I1{}, I0{}, 0);
             // sub-step 1
             PIN_SET(1);
@@ -448,7 +403,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
         body(std::false_type{}, std::false_type{}, t);
         }   // NST == 2
 
-        DW_TRACE(2);
         // ---- optional (dw_debug_set key 11 bit 128, OFF by default): the NEXT tile's first operand tile, requested before
         // this tile's epilogue.  The epilogue's LDS patches live in operand buffer 1 only (swizzled, unpadded: 8 waves x
         // 8 KiB), so the next job's tile 0 can stream into buffer 0 while this tile's results are transposed and stored;
@@ -459,7 +413,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
         // comes first after the epilogue's 32 stores sits out their acknowledgement; operand latency was never what the
         // prologue waited for.  Hence off.
         prefetched = false;
-        if constexpr (ASMDMA && DBG == 0 && TN == 64 && BM >= 256) {
+        if constexpr (TN == 64 && BM >= 256) {
             const int nxt = jobs.dynamic ? job_slot[(jobs.iter + 1) & 1] : jobs.cur + jobs.step;
             if ((p.stage_next & 128) && (nt & 1) == 0 && nt >= 2 && nxt < jobs.cnt && tile_in && !p.zgrad && !p.r) {
                 int tm2, tn2, ks2;
@@ -479,26 +433,16 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN / 4) void gemm_wp_kernel(cons
         }
         // (the eight swizzled 8 KiB patches fill operand buffer 1 of the 256- / 320-row tiles; the 128-row tile's 48 KiB stages are
         // smaller than that: its patches start at buffer 0 and run into buffer 1)
-        if (!(p.stage_next & 16)) gemm_epilogue<FM, FN, TN, (BM == 320 ? EPF : 8), GemmNoHook, TN == 64>(p, acc, smem + (TN == 64 && STAGE >= NW * 8192 ? STAGE : 0), wave, lane, m0, wm0, n0, wn0, ks, GemmNoHook(), tile_in ? bias_lds : nullptr,
-                                                           (p.trace && tid == 0 && jobs.iter < 8) ? p.trace + ((long)blockIdx.x * 8 + jobs.iter) * 8 : nullptr);
-        else { float t = 0.f;
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) t += acc[i][j][r];
-            if (t == 123.456f) *(float*)p.c = t; }
-        DW_TRACE(3);
+        gemm_epilogue<FM, FN, TN, (BM == 320 ? EPF : 8), GemmNoHook, TN == 64>(p, acc, smem + (TN == 64 && STAGE >= NW * 8192 ? STAGE : 0), wave, lane, m0,
+                                                                          wm0, n0, wn0, ks, GemmNoHook(), tile_in ? bias_lds : nullptr);
         gemm_lds_barrier();   // the LDS patches are reused as operand buffers by the next job (no vmcnt wait: the stores and
                               // the next tile's operand DMA stay in flight)
-        DW_TRACE(4);
         gemm_jobs_advance(jobs, job_slot);
     }
     gemm_jobs_end(p, jobs);
 }
 
-template <bool TA, bool TB, int WM, int WN, bool ASMDMA = true, int DBG = 0, int BM = 256, int NST = 2>
+template <bool TA, bool TB, int WM, int WN, int BM = 256, int NST = 2>
 static int launch_wp(const GemmP& p0, hipStream_t s) {
     GemmP p = p0;
     const int tiles_m = (p.m + BM - 1) / BM;
@@ -507,7 +451,7 @@ static int launch_wp(const GemmP& p0, hipStream_t s) {
     p.strip = gemm_strip_width(p.k, p.tiles_n, p.strip);
     int nblk = p.nwg * p.split_k;
     if (nblk > g_gemm_cus) nblk = g_gemm_cus;
-    hipLaunchKernelGGL((gemm_wp_kernel<TA, TB, WM, WN, ASMDMA, DBG, BM, NST>), dim3(nblk), dim3(64 * WM * WN), 0, s, p);
+    hipLaunchKernelGGL((gemm_wp_kernel<TA, TB, WM, WN, true, 0, BM, NST>), dim3(nblk), dim3(64 * WM * WN), 0, s, p);
     DW_CHECK_LAUNCH();
     return DW_OK;
 }

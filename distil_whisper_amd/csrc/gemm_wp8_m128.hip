@@ -4,5 +4,5 @@
 // in a THREE-stage ring (gemm_wp.h NST = 3: a sub-step of this tile is four MFMAs, too short for the two-stage lead) -- the
 // lock-step 128 x 128 kernel of gemm_kernel.h waits out every operand tile.
 #include "gemm_wp.h"
-int dw_gemm_wp8_nn128_launch(const GemmP& p, hipStream_t s) { return launch_wp<false, false, 2, 4, true, 0, 128, 3>(p, s); }
-int dw_gemm_wp8_nt128_launch(const GemmP& p, hipStream_t s) { return launch_wp<false, true, 2, 4, true, 0, 128, 3>(p, s); }
+int dw_gemm_wp8_nn128_launch(const GemmP& p, hipStream_t s) { return launch_wp<false, false, 2, 4, 128, 3>(p, s); }
+int dw_gemm_wp8_nt128_launch(const GemmP& p, hipStream_t s) { return launch_wp<false, true, 2, 4, 128, 3>(p, s); }

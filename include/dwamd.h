@@ -307,29 +307,20 @@ int dw_decode_step(const DwDecodeStep* d, void* stream);
  * Runs ds_read_b64_tr_b16 on a known LDS image: out int32 [64][4] = element ids received by each lane. */
 int dw_selftest_tr16(int32_t* out, void* stream);
 /* Tuning knobs for kernel A/B experiments and tests; not part of the hot path (defaults are the measured best).
- *   key 0   GEMM kernel selection, bit mask (default 2163 = 115 | 2048): bits 0-1 base 16-wave tile kernel; bit 2
- *           phase-pipelined kernel for dX GEMMs with K >= 3840; bits 4/5/6 8-wave software-pipelined kernel for row-major /
- *           k-major-B / both-k-major operands; bit 7 phase-pipelined kernel for every dX GEMM; bit 8 row-major kernel with
- *           the operand DMA through the compiler builtin (A/B reference); bit 11 (2048) 320 x 256 block tiles for
- *           row-major A where they pay (M % 320 == 0, N % 256 == 0; K >= 2560, or row-major B with N >= 2560; a grid
- *           of one round of them instead of 128-tiles), bit 12 (4096) wherever eligible.  All bit-identical.
- *           Bits 9 / 10 (512 / 1024): main-loop ablations of the row-major kernel for profiling -- no fragment reads /
- *           no operand DMA in the K loop (WRONG results by construction; tools/gemm_overhead.py, gemm_power_probe.py).
- *   key 1   rasterisation strip width override (0 = rule);   key 6  strip L2 budget in 512 KiB units (default 8)
- *   key 2   persistent workgroups on/off;   key 9  persistent grid size in CUs (multiple of 8, default 256)
- *   key 10  dynamic per-XCD tile hand-out (default 1);   key 11  profiling: bit 4 (16) makes the software-pipelined
- *           kernels skip their epilogue (nothing is stored; tools/gemm_overhead.py); other bits unused (default 1)
+ *   key 0   GEMM kernel choice (csrc/gemm.hip gemm_choose): 0 = the default rule; 1 = the reference kernels only (16-wave
+ *           256 x 256 tile, 8-wave 128 x 128 tile for small grids); 2 = the default rule, and the 320 x 256 tile wherever it is
+ *           eligible (row-major A, M % 320 == 0, N % 256 == 0, one K slice).  Every kernel gives bit-identical results.
+ *   key 1   rasterisation strip width override (0 = rule);   key 6  strip L2 budget in 512 KiB units (default 4)
+ *   key 9   persistent grid size in CUs (multiple of 8, default 256)
+ *   key 10  dynamic per-XCD tile hand-out (default 1);   key 11  GEMM staging: bit 7 (128) requests the next tile's first
+ *           operand tile before the epilogue at any K (the rule does so for K <= 1024); bit 4 (16) makes the 16x16x32
+ *           kernels skip their epilogue (profiling: nothing is stored); other bits unused (default 1)
  *   key 3   attention backward variant (bit 0 dQ, bit 1 dK/dV fast tile staging, bit 2 dK/dV at 3 waves per SIMD -- bits 1
  *           and 2 apply to the NON-causal dK/dV kernel only: the causal launch always runs two waves per SIMD; default 5);   key 4  single-query attention kernel (bit 0 on [default], bit 1 all-loads-up-front variant)
  *   key 5   log-mel DFT on the matrix cores (default 1);   key 7  decode-step fusions off (bit 0 LayerNorm-on-load,
  *           bit 1 K/V append, bit 2 self-attention with its q / k / v projection inside, bit 3 cross-attention with its q
  *           projection inside; default 4);   key 8  token-step GEMVs, bit mask (default 5): bit 0 wide LM-head kernel; bit 1 LayerNorm-on-load kernels keep one
  *           column block per workgroup; bits 2-3 columns per workgroup of the projections back to d_model (4: 8, 0: 4, 12: 16)
- *   key 19  row-major 256-row GEMMs run main-loop ablation `value` (1 no fragment reads, 2 no operand DMA, 3 both, 4 DMA that
- *           always hits L2; WRONG results by construction; tools/gemm_dma_diag.py);   key 20  bit mask: software-pipelined GEMM
- *           kernels on v_mfma_f32_16x16x32_bf16 (1 row-major, 2 k-major B, 4 both k-major, 32 row-major with K <= 2560 and
- *           N >= 3840 on the 256-row tile; default 36; bit-identical results;
- *           8 / 16: the four-wave 128 x 128-per-wave experiment for row-major / k-major B, gemm_wp16_w4.hip)
  *   key 21  LayerNorm kernels: bit 0 persistent fp32-input forward with next-row prefetch (bits 8-11: workgroups per CU),
  *           bit 1 backward with next-row / residual-gradient prefetch at two waves per SIMD (default 3; tools/ln_ab.py)
  *   key 22  wide row-major 256-row launches hand a partial last row block (<= 128 rows) to the 128-tile kernel when the full
@@ -337,12 +328,9 @@ int dw_selftest_tr16(int32_t* out, void* stream);
  *   key 23  attention forward: threshold (in powers of two) by which a tile maximum must exceed the running reference of
  *           the online softmax before the reference moves (default 8; 0 = the exact running maximum, the A/B leg of
  *           tests/test_sharp_parity_gpu.py)
- *   key 24  128-tile launches on the four-wave tile (2 x 2 waves of 64 x 64; 1 plain K loop, 2 register double buffer;
- *           default 0 = eight waves of 64 x 32; bit-identical)
  *   key 25  outputs with fewer than two rounds of 256-row tiles (the decoders' M = 32 x live positions): kernel chosen by the
  *           rounds of the CUs it needs among 128 x 256 tiles in a three-stage operand ring (csrc/gemm_wp8_m128.hip), 256 x 256
- *           on 16x16x32 and 320 x 256 (default 1; 0 = the lock-step 128 x 128 kernel; 2 = as 1, and DwGemm.tile 129 forces the
- *           128-row kernel at any size; bit-identical)
+ *           on 16x16x32 and 320 x 256 (default 1; 0 = the lock-step 128 x 128 kernel; bit-identical)
  *   key 26  non-causal attention forward on the software-pipelined kernel (scores of key tile t+1 under the softmax of tile
  *           t, three K / V stages; 1: three waves per SIMD, 2: two).  Default 0: measured 8 % / 15 % SLOWER than the four-waves-
  *           per-SIMD kernel at the encoder shape (tools/attn_pipe_ab.py), bit-identical -- kept as the A/B of that design

@@ -62,7 +62,7 @@ def test_hot_loops_have_no_flat_accesses_and_no_scratch_traffic(tu, loops_at_lea
 # Whole-kernel scratch budgets of the kernels the default dispatch launches (round-4 review: the 320-row kernels sat on a register
 # cliff -- 100 B of scratch, 163 scratch instructions, one reload behind a vmcnt(0) per row group of the fp32-residual walk; a
 # compiler bump could cost 8 % of the step unnoticed).  Since round 5 the epilogue re-derives its lane addresses per tile
-# (gemm_common.h DW_EPI_LAUNDER) and the budgets are: nothing for the 256-row kernels and the attention kernels, 16 B / 6
+# (gemm_common.h, the opaque redefinition of `lane`) and the budgets are: nothing for the 256-row kernels and the attention kernels, 16 B / 6
 # instructions (the run-time-flavour walk's end and the kernel exit) for the 320-row kernels.
 SCRATCH_BUDGET = [
     ("attention", r"attn_(fwd_kernel<(true|false), 4, 0>|bwd_dkv_kernel<true, false, 2, 4>)", 0, 0),

@@ -129,24 +129,23 @@ def test_gemm_epilogues(ops, ref, tile):
         ops._chk(ops.lib.dw_gemm_bf16(ctypes.byref(d), ops._stream()), "z_is_gelu_grad without act")
 
 
-@pytest.mark.parametrize("variant,ta,tb", [(131, False, True), (19, False, False), (35, False, True), (67, True, True)])
-def test_gemm_pipelined_variants_are_bit_identical(ops, ref, variant, ta, tb):
-    """gemm_phased.hip (variant bit 7: counted-vmcnt, slot-staggered main loop, region-major LDS image) and the 8-wave
-    software-pipelined kernels of gemm_wp.h (bits 4-6: register double-buffered fragments, pinned MFMA / LDS / DMA
-    interleave, buffer-addressed operand DMA) against the plain 16-wave kernel: same k order per accumulator, so every
-    output bit must agree -- each operand layout the kernels are built for, ragged M/N edges, 1..5 K tiles (prologue /
-    tail wait counts), persistent job walk (> 256 tiles), fused epilogue, split-K slices, repeated launches (race
-    screen)."""
+@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, True)])
+def test_gemm_pipelined_variants_are_bit_identical(ops, ref, ta, tb):
+    """Each operand layout's default kernel (dw_debug_set key 0 = 0: the software-pipelined kernels of gemm_wp.h / gemm_wp16.h --
+    register double-buffered fragments, pinned MFMA / LDS / DMA interleave, buffer-addressed operand DMA) against the reference
+    kernels (key 0 = 1: the plain 16-wave kernel): same k order per accumulator, so every output bit must agree -- ragged M/N
+    edges, 1..5 K tiles (prologue / tail wait counts), persistent job walk (> 256 tiles), fused epilogue, split-K slices,
+    repeated launches (race screen)."""
     try:
         for M, N, K in ((520, 392, 64), (520, 392, 128), (304, 512, 192), (776, 1024, 320), (4096, 4608, 256),
                         (8 * 1500, 1280, 1280)):
             a = rnd((K, M) if ta else (M, K), 0.5, seed=41)
             b = rnd((K, N) if tb else (N, K), 0.1, seed=42)
             bias = rnd((N,), 0.5, torch.float32, seed=43)
-            ops.lib.dw_debug_set(0, 3)
+            assert ops.lib.dw_debug_set(0, 1) == 0
             want = ops.gemm(a, b, trans_a=ta, trans_b=tb, bias=bias, act=1, tile=256).clone()
             want32 = ops.gemm(a, b, trans_a=ta, trans_b=tb, out_dtype=torch.float32, tile=256).clone()
-            ops.lib.dw_debug_set(0, variant)
+            ops.lib.dw_debug_set(0, 0)
             for rep in range(3):
                 got = ops.gemm(a, b, trans_a=ta, trans_b=tb, bias=bias, act=1, tile=256)
                 assert torch.equal(got, want), (M, N, K, rep, (got.float() - want.float()).abs().max().item())
@@ -155,20 +154,20 @@ def test_gemm_pipelined_variants_are_bit_identical(ops, ref, variant, ta, tb):
             assert relerr(want32, ref.gemm(a, b, trans_a=ta, trans_b=tb, out_dtype=torch.float32)) < 1e-5
         if ta and tb:       # weight-gradient form: K = tokens, split into slices, fp32 partials + deterministic reduce
             a, b = rnd((6400, 1280), 0.5, seed=44), rnd((6400, 384), 0.5, seed=45)
-            ops.lib.dw_debug_set(0, 3)
+            ops.lib.dw_debug_set(0, 1)
             want = torch.zeros(1280, 384, device="cuda")
             ops.gemm(a, b, trans_a=True, trans_b=True, out_dtype=torch.float32, out=want, atomic_acc=True, split_k=5)
-            ops.lib.dw_debug_set(0, variant)
+            ops.lib.dw_debug_set(0, 0)
             got = torch.zeros(1280, 384, device="cuda")
             ops.gemm(a, b, trans_a=True, trans_b=True, out_dtype=torch.float32, out=got, atomic_acc=True, split_k=5)
             assert torch.equal(got, want)
     finally:
-        ops.lib.dw_debug_set(0, 2163)
+        ops.lib.dw_debug_set(0, 0)
 
 
 @pytest.mark.parametrize("tb", [False, True])
 def test_gemm_320_row_tiles_are_bit_identical(ops, ref, tb):
-    """gemm_wp8_m320.hip (variant bit 2048): 320 x 256 block tiles, 160 x 64 per wave, one address register per operand
+    """gemm_wp8_m320.hip (dw_debug_set key 0 = 2 forces it wherever it is eligible): 320 x 256 block tiles, 160 x 64 per wave, one address register per operand
     with the piece stride in the scalar offset.  Same k order per accumulator as the 16-wave 256-row kernel, so every
     output bit must agree: both B layouts, 1..5 and 20 K tiles, one and several tile rounds (persistent walk), every
     fused epilogue flavour (bias + GELU, stored gelu', GELU' input, bf16 / fp32 residual, fp32 output), repeated launches.
@@ -186,11 +185,11 @@ def test_gemm_320_row_tiles_are_bit_identical(ops, ref, tb):
                         dict(bias=bias, residual=r32, out_dtype=torch.float32), dict(zgrad=zin), dict(bias=bias, act=1, want_z=True),
                         dict(bias=bias, act=1, want_z="grad"), dict(zgrad=zin.to(torch.float16)))
             want = []
-            ops.lib.dw_debug_set(0, 3)
+            ops.lib.dw_debug_set(0, 1)
             for f in flavours:
                 o = ops.gemm(a, b, trans_b=tb, tile=256, **f)
                 want.append([t.clone() for t in o] if isinstance(o, tuple) else [o.clone()])
-            ops.lib.dw_debug_set(0, 115 | 2048 | 4096)
+            assert ops.lib.dw_debug_set(0, 2) == 0
             for rep in range(2):
                 for f, w in zip(flavours, want):
                     o = ops.gemm(a, b, trans_b=tb, tile=256, **f)
@@ -203,18 +202,18 @@ def test_gemm_320_row_tiles_are_bit_identical(ops, ref, tb):
         if not tb:
             a, b = rnd((14400, 1280), 0.5, seed=59), rnd((1280, 1280), 0.1, seed=60)
             bias, r16 = rnd((1280,), 0.5, torch.float32, seed=61), rnd((14400, 1280), 1.0, seed=62)
-            ops.lib.dw_debug_set(0, 3)
+            ops.lib.dw_debug_set(0, 1)
             w = ops.gemm(a, b, bias=bias, residual=r16).clone()              # 128-tiles
-            ops.lib.dw_debug_set(0, 2163)
+            ops.lib.dw_debug_set(0, 0)
             assert torch.equal(ops.gemm(a, b, bias=bias, residual=r16), w)   # one round of 320-row tiles
         # not eligible: ragged M / N -> the 256-row kernels, same bits
         a, b = rnd((1000, 128), 0.5, seed=57), rnd((128, 304) if tb else (304, 128), 0.1, seed=58)
-        ops.lib.dw_debug_set(0, 3)
+        ops.lib.dw_debug_set(0, 1)
         w = ops.gemm(a, b, trans_b=tb, tile=256).clone()
-        ops.lib.dw_debug_set(0, 115 | 2048 | 4096)
+        ops.lib.dw_debug_set(0, 2)
         assert torch.equal(ops.gemm(a, b, trans_b=tb, tile=256), w)
     finally:
-        ops.lib.dw_debug_set(0, 2163)
+        ops.lib.dw_debug_set(0, 0)
 
 
 @pytest.mark.gpu
@@ -258,14 +257,19 @@ def test_gemm_small_m_rule_is_bit_identical(ops, ref, tb):
 
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, True)])
 def test_gemm_16x16x32_main_loop_is_bit_identical(ops, ref, ta, tb):
-    """gemm_wp16.h: the software-pipelined main loop on v_mfma_f32_16x16x32_bf16 (dw_debug_set key 20; the default for the
-    weight-gradient layout and for wide row-major outputs) -- 16 x 32 fragments under their own LDS swizzles, the k-major image through ds_read_b64_tr_b16 in
-    the 16 x 16 x 32 operand order, accumulators as 16 x 16 blocks through the LAY = 16 epilogue.  The hardware accumulates a
-    32-deep instruction in the order two 16-deep ones do, so every output bit agrees with the 32x32x16 kernels: each
-    layout, 256-row and 320-row tiles, ragged edges, 1..5 and 20 K tiles, persistent walk, every epilogue flavour of the
-    step (both epilogue walks), split-K slices, repeated launches."""
+    """gemm_wp16.h: the software-pipelined main loop on v_mfma_f32_16x16x32_bf16 (the default for the weight-gradient layout, for
+    wide short-K row-major outputs -- K <= 2560, N >= 3840, bf16 out, no side input -- and for the small-M rule's 256-row
+    launches) -- 16 x 32 fragments under their own LDS swizzles, the k-major image through ds_read_b64_tr_b16 in the 16 x 16 x 32
+    operand order, accumulators as 16 x 16 blocks through the LAY = 16 epilogue.  The hardware accumulates a 32-deep instruction
+    in the order two 16-deep ones do, so every output bit agrees with the reference 32x32x16 kernels (dw_debug_set key 0 = 1):
+    each layout, ragged edges, 1..5 and 20 K tiles, persistent walk, every epilogue flavour of the step (both epilogue walks),
+    split-K slices, repeated launches.  The row-major shapes with N >= 3840 and K <= 2560 are the ones the rule gives the
+    16x16x32 kernel (ragged M / N, 1..5 K tiles); the others check the default kernel of the layout against the reference."""
     try:
         shapes = ((520, 392, 64), (776, 1024, 320), (640, 512, 128), (3200, 1280, 192), (320 * 30, 3840, 256), (8 * 1500, 1280, 1280))
+        if not ta and not tb:
+            shapes += ((520, 3848, 64), (776, 3840, 128), (1100, 4100, 192), (2000, 5120, 256), (4104, 3900, 320), (8804, 3840, 320),
+                       (8 * 1500, 3840, 1280))
         for M, N, K in shapes:
             a = rnd((K, M) if ta else (M, K), 0.5, seed=71)
             b = rnd((K, N) if tb else (N, K), 0.1, seed=72)
@@ -276,35 +280,30 @@ def test_gemm_16x16x32_main_loop_is_bit_identical(ops, ref, ta, tb):
             flavours = (dict(), dict(bias=bias), dict(bias=bias, act=1), dict(out_dtype=torch.float32), dict(bias=bias, residual=r16),
                         dict(bias=bias, residual=r32, out_dtype=torch.float32), dict(zgrad=zin), dict(bias=bias, act=1, want_z="grad"))
             want = []
-            ops.lib.dw_debug_set(20, 0)
+            ops.lib.dw_debug_set(0, 1)
             for f in flavours:
                 o = ops.gemm(a, b, trans_a=ta, trans_b=tb, tile=256, **f)
                 want.append([t.clone() for t in o] if isinstance(o, tuple) else [o.clone()])
-            # 7: every layout on 16x16x32; 7 | 32: + the 256-row tile where the 320-row one is the rule's choice; 8 | 16: the four-wave
-            # layout (one wave per SIMD, 128 x 128 per wave, accumulators pinned to AGPRs) for the row-major-A layouts
-            for mask in ((7, 7 | 32) if ta else (7, 7 | 32, 8 | 16)):
-                ops.lib.dw_debug_set(20, mask)
-                if mask & 8: ops.lib.dw_debug_set(0, 115)          # (the four-wave kernels take the 256-row tile's place)
+            ops.lib.dw_debug_set(0, 0)
+            for tile in ((256, 0) if not ta and not tb else (256,)):     # (tile 0: the automatic choice; M = 8 804 takes the row tail)
                 for rep in range(2):
                     for f, w in zip(flavours, want):
-                        o = ops.gemm(a, b, trans_a=ta, trans_b=tb, tile=256, **f)
+                        o = ops.gemm(a, b, trans_a=ta, trans_b=tb, tile=tile, **f)
                         o = list(o) if isinstance(o, tuple) else [o]
                         for g_, w_ in zip(o, w):
-                            assert torch.equal(g_, w_), (M, N, K, ta, tb, mask, sorted(f), rep, (g_.float() - w_.float()).abs().max().item())
-                ops.lib.dw_debug_set(0, 2163)
+                            assert torch.equal(g_, w_), (M, N, K, ta, tb, tile, sorted(f), rep, (g_.float() - w_.float()).abs().max().item())
             assert relerr(want[3][0], ref.gemm(a, b, trans_a=ta, trans_b=tb, out_dtype=torch.float32)) < 1e-5
         if ta and tb:       # weight-gradient form with K slices
             a, b = rnd((6400, 1280), 0.5, seed=77), rnd((6400, 384), 0.5, seed=78)
             outs = []
-            for v in (0, 7):
-                ops.lib.dw_debug_set(20, v)
+            for v in (1, 0):
+                ops.lib.dw_debug_set(0, v)
                 o = torch.zeros(1280, 384, device="cuda")
                 ops.gemm(a, b, trans_a=True, trans_b=True, out_dtype=torch.float32, out=o, atomic_acc=True, split_k=5)
                 outs.append(o)
             assert torch.equal(outs[0], outs[1])
     finally:
-        ops.lib.dw_debug_set(20, 36)
-        ops.lib.dw_debug_set(0, 2163)
+        ops.lib.dw_debug_set(0, 0)
 
 
 def test_gemm_dynamic_job_handout_is_invisible(ops, ref):
@@ -336,8 +335,8 @@ def test_gemm_dynamic_job_handout_is_invisible(ops, ref):
 
 def test_gemm_next_tile_staging_under_the_epilogue_is_invisible(ops, ref):
     """The software-pipelined kernels request the NEXT tile's first operand block into LDS buffer 0 while the epilogue
-    of the current tile runs out of buffer 1 (dw_debug_set key 11; even K-tile counts only).  Same bits with it on and
-    off: every operand layout, 2 / 4 / 20 K tiles (and an odd count, which must not stage), more tiles than
+    of the current tile runs out of buffer 1 (K <= 1024, or any K with dw_debug_set key 11 = 128; even K-tile counts only).
+    Same bits as the reference kernels (dw_debug_set key 0 = 1), which never stage: every operand layout, 2 / 4 / 20 K tiles (and an odd count, which must not stage), more tiles than
     workgroups with ragged edges, static and dynamic hand-out, epilogues with and without side inputs, repeated
     launches (race screen)."""
     try:
@@ -352,16 +351,18 @@ def test_gemm_next_tile_staging_under_the_epilogue_is_invisible(ops, ref):
                         lambda: ops.gemm(a, b, trans_a=ta, trans_b=tb, bias=bias, residual=res,
                                          out_dtype=torch.float32, tile=256),
                         lambda: ops.gemm(a, b, trans_a=ta, trans_b=tb, zgrad=zg, tile=256))
-                ops.lib.dw_debug_set(11, 0)
+                ops.lib.dw_debug_set(0, 1)
                 want = [f().clone() for f in runs]
-                ops.lib.dw_debug_set(11, 1)
-                for dyn in (1, 0):
-                    ops.lib.dw_debug_set(10, dyn)
-                    for rep in range(2):
-                        for f, w in zip(runs, want):
-                            assert torch.equal(f(), w), (ta, tb, M, N, K, dyn)
+                ops.lib.dw_debug_set(0, 0)
+                for k11 in (1, 128):
+                    ops.lib.dw_debug_set(11, k11)
+                    for dyn in (1, 0):
+                        ops.lib.dw_debug_set(10, dyn)
+                        for rep in range(2):
+                            for f, w in zip(runs, want):
+                                assert torch.equal(f(), w), (ta, tb, M, N, K, k11, dyn)
     finally:
-        ops.lib.dw_debug_set(10, 1); ops.lib.dw_debug_set(11, 1)
+        ops.lib.dw_debug_set(0, 0); ops.lib.dw_debug_set(10, 1); ops.lib.dw_debug_set(11, 1)
 
 
 @pytest.mark.parametrize("xdtype", [torch.float32, torch.bfloat16])

@@ -1,6 +1,6 @@
 """The step's GEMM launches with their REAL epilogues, per kernel variant (DW_VARIANTS = JSON list of [dw_debug_set key 0
-value, key 11 value]; key 11: 1 = default, 65 = one run-time epilogue walk for every flavour, 17 = no epilogue).  Operand A and the output rotate over three buffers (369 MB of A: past the Infinity Cache, as in
-the step).  Every variant is checked bit for bit against the 16-wave reference kernel (variant 3).  Round 3 used it for
+value, key 11 value]; key 0: 0 = default rule, 2 = 320-row tile where eligible; key 11: 1 = default, 129 = next-tile staging at any K).  Operand A and the output rotate over three buffers (369 MB of A: past the Infinity Cache, as in
+the step).  Every variant is checked bit for bit against the 16-wave reference kernel (key 0 = 1).  Round 3 used it for
 the two-workgroups-per-CU experiment (profiles/r3_gemm_two_workgroups_per_cu.md; that kernel is not in the build)."""
 import os, sys, json, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,7 +28,7 @@ cases = [  # name, M, N, K, trans_b, kwargs-builder
 only = os.environ.get("DW_CASES")
 if only:
     cases = [c for c in cases if any(k in c[0] for k in only.split(","))]
-variants = json.loads(os.environ.get("DW_VARIANTS", "[[2163,1],[2163,65]]"))
+variants = json.loads(os.environ.get("DW_VARIANTS", "[[0,1],[0,129]]"))
 rounds = int(os.environ.get("DW_ROUNDS", "3"))
 def run(a, b, out, tb, kw):
     kw = dict(kw)
@@ -44,7 +44,7 @@ for name, m, N, K, tb, mk in cases:
         kw["zgrad"] = kw["zgrad"][:m]
     odt = kw.get("out_dtype", torch.bfloat16)
     outs = [torch.empty(m, N, device="cuda", dtype=odt) for _ in range(3)]
-    ops.lib.dw_debug_set(0, 3); ops.lib.dw_debug_set(11, 1)
+    ops.lib.dw_debug_set(0, 1); ops.lib.dw_debug_set(11, 1)
     r = run(As[0], b, outs[0], tb, kw)
     ref = (r[0] if isinstance(r, tuple) else r).clone()
     refz = r[1].clone() if isinstance(r, tuple) else None
@@ -74,4 +74,4 @@ for name, m, N, K, tb, mk in cases:
     print(f"{name:34s} us/launch {line}  best {best} ({base / line[best]:.3f}x, {2.0 * m * N * K / line[best] / 1e6:.0f} TF/s)", flush=True)
     del As, outs, kw, b
     torch.cuda.empty_cache()
-ops.lib.dw_debug_set(0, 2163); ops.lib.dw_debug_set(11, 1)
+ops.lib.dw_debug_set(0, 0); ops.lib.dw_debug_set(11, 1)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build distil_whisper_amd/libdwamd_base.so from another commit's csrc (default HEAD) for same-process A/B runs
-# (tools/ab_step.py field 13, tools/attn_ab_libs.py).  The file is git-ignored.
+# (tools/ab_keys.py `lib`, tools/attn_ab_libs.py).  The file is git-ignored.
 set -e
 REV=${1:-HEAD}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -17,7 +17,7 @@ for M in [int(x) for x in os.environ.get("MS", "4480,4258,7136,14304").split(","
               (f"M={M} fc2 N=1280 K=5120 bias+resbf16", M, 1280, 5120, False, dict(bias=bias[1280], residual=resb)),
               (f"M={M} dX N=1280 K=3840 plain", M, 1280, 3840, True, {}),
               (f"M={M} dX N=1280 K=5120 plain", M, 1280, 5120, True, {})]
-variants = [("auto", 0, 0), ("t128", 128, 0), ("wp128", 129, 0), ("t256 32x32", 256, 0), ("t256 16x16", 256, 7)]
+variants = [("auto", 0), ("t128", 128), ("wp128", 129), ("t256", 256)]
 for name, M, N, K, tb, kw in cases:
     a = rnd((M, K)); b = rnd((K, N) if tb else (N, K), 0.05)
     ref = ops.gemm(a, b, trans_b=tb, tile=128, **kw)
@@ -25,8 +25,7 @@ for name, M, N, K, tb, kw in cases:
     same = bool(torch.equal(ref, got))
     res = {v[0]: [] for v in variants}
     for r in range(4):
-        for label, tile, mi in variants:
-            ops.lib.dw_debug_set(20, mi if mi else 36)
+        for label, tile in variants:
             for _ in range(2): ops.gemm(a, b, trans_b=tb, tile=tile, **kw)
             torch.cuda.synchronize()
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -35,4 +34,3 @@ for name, M, N, K, tb, kw in cases:
             e.record(); torch.cuda.synchronize()
             res[label].append(s.elapsed_time(e) / 20 * 1e3)
     print(f"{name:44s} identical={same} ", {k: f"{sorted(v)[len(v)//2]:.1f}" for k, v in res.items()}, flush=True)
-ops.lib.dw_debug_set(20, 36)

@@ -1,5 +1,5 @@
-"""Clock and socket power under a sustained GEMM stream: the normal kernel, the main-loop ablations of gemm_wp8_dbg.hip
-(MFMA only / no fragment reads / no operand DMA) and the vendor library.  Is the matrix pipe clock-throttled at full duty?"""
+"""Clock and socket power under a sustained GEMM stream: the library's kernel and the vendor library, with real and with zero
+operands.  Is the matrix pipe clock-throttled at full duty?"""
 import os, subprocess, sys, threading, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distil_whisper_amd.ops_hip import HipOps
@@ -29,19 +29,11 @@ def run(name, fn, secs=5.0):
     dt = time.time() - t0
     stop[0] = True; th.join()
     print(f"{name}: {2.0*M*N*K*n/dt/1e12:.0f} TFLOP/s sustained; (power W, sclk): " + " ".join(f"{p[0] if p else '?'}/{c[0] if c else '?'}" for p, c in samples[2:14]), flush=True)
-def mine(v, k11):
-    def f():
-        ops.gemm(a, b, out=out, tile=256)
-    ops.lib.dw_debug_set(0, v); ops.lib.dw_debug_set(11, k11)
-    return f
-for name, v, k11 in (("full kernel", 115, 1), ("no epilogue", 115, 17), ("MFMA only, no epilogue", 115 | 1536, 17),
-                     ("no DMA, no epilogue", 115 | 1024, 17), ("no fragment reads, no epilogue", 115 | 512, 17)):
-    run(name, mine(v, k11))
-ops.lib.dw_debug_set(0, 2163); ops.lib.dw_debug_set(11, 1)
+def mine():
+    return lambda: ops.gemm(a, b, out=out, tile=256)
+run("full kernel", mine())
 out2 = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
 run("vendor (torch.matmul)", lambda: torch.matmul(a, b.t(), out=out2))
 z = torch.zeros_like(a); zb = torch.zeros_like(b)
 a.copy_(z); b.copy_(zb)
-run("full kernel, zero operands", mine(115, 1))
-run("MFMA only, zero operands", mine(115 | 1536, 17))
-ops.lib.dw_debug_set(0, 2163); ops.lib.dw_debug_set(11, 1)
+run("full kernel, zero operands", mine())

@@ -14,9 +14,9 @@ cases = [("qkv bias N=2304 K=768", 3 * D, D, False, dict(bias=bias[3 * D])),
          ("fc2 bias+res32 N=768 K=3072", D, F, False, dict(bias=bias[D], residual=res32, out_dtype=torch.float32)),
          ("dX qkv plain N=768 K=2304", D, 3 * D, True, {}), ("dX fc1 plain N=768 K=3072", D, F, True, {}),
          ("dX out plain N=768 K=768", D, D, True, {})]
-# (label, key-0 variant, tile argument, key-11 value)
-variants = [("default", 2163, 0, 1), ("256-row 8-wave", 115, 256, 1), ("16-wave", 3, 256, 1), ("tile128", 2163, 128, 1),
-            ("320 forced", 2163 | 4096, 256, 1), ("default+next-tile prefetch", 2163, 0, 129)]
+# (label, key-0 value (0 default rule, 1 reference kernels, 2 320-row tile where eligible), tile argument, key-11 value)
+variants = [("default", 0, 0, 1), ("256-row default", 0, 256, 1), ("16-wave", 1, 256, 1), ("tile128", 0, 128, 1),
+            ("320 forced", 2, 256, 1), ("default+next-tile prefetch", 0, 0, 129)]
 for name, N, K, tb, kw in cases:
     a = rnd((M, K)); b = rnd((K, N) if tb else (N, K), 0.05)
     res = {v[0]: [] for v in variants}
@@ -31,4 +31,4 @@ for name, N, K, tb, kw in cases:
             e.record(); torch.cuda.synchronize()
             res[label].append(2.0 * M * N * K / (s.elapsed_time(e) / 10 * 1e-3) / 1e12)
     print(f"{name:30s}", {k: f"{sorted(v)[len(v)//2]:.0f}" for k, v in res.items()}, flush=True)
-ops.lib.dw_debug_set(0, 2163); ops.lib.dw_debug_set(11, 1)
+ops.lib.dw_debug_set(0, 0); ops.lib.dw_debug_set(11, 1)

@@ -14,13 +14,12 @@ for M in (7136, 4258 + 222, 14304):
               (f"M={M} fc1 N=5120 K=1280 gelu", M, 5120, 1280, False, dict(bias=bias[5120], act=1)),
               (f"M={M} fc2 N=1280 K=5120 bias+res32", M, 1280, 5120, False, dict(bias=bias[1280], residual=res32, out_dtype=torch.float32)),
               (f"M={M} dX N=1280 K=3840 plain", M, 1280, 3840, True, {})]
-variants = [("auto", 0, 0), ("tile128", 128, 0), ("tile256 32x32", 256, 0), ("tile256 16x16", 256, 7)]
+variants = [("auto", 0), ("tile128", 128), ("tile256", 256)]
 for name, M, N, K, tb, kw in cases:
     a = rnd((M, K)); b = rnd((K, N) if tb else (N, K), 0.05)
     res = {v[0]: [] for v in variants}
     for r in range(4):
-        for label, tile, mi in variants:
-            ops.lib.dw_debug_set(20, mi if mi else 4)
+        for label, tile in variants:
             for _ in range(2): ops.gemm(a, b, trans_b=tb, tile=tile, **kw)
             torch.cuda.synchronize()
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -29,4 +28,3 @@ for name, M, N, K, tb, kw in cases:
             e.record(); torch.cuda.synchronize()
             res[label].append(s.elapsed_time(e) / 20 * 1e3)
     print(f"{name:44s}", {k: f"{sorted(v)[len(v)//2]:.1f}us" for k, v in res.items()}, flush=True)
-ops.lib.dw_debug_set(20, 4)

@@ -7,7 +7,7 @@ ops = HipOps("cuda:0")
 M, N, K = 48000, int(os.environ.get("N", 3840)), int(os.environ.get("K", 1280))
 a = torch.randn(M, K, device="cuda").bfloat16(); b = (torch.randn(N, K, device="cuda") * 0.05).bfloat16()
 out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-variants = [int(v) for v in os.environ.get("DW_VARIANTS", "3,19").split(",")]
+variants = [int(v) for v in os.environ.get("DW_VARIANTS", "1,0").split(",")]     # dw_debug_set key 0 values
 chunks, per = int(os.environ.get("CHUNKS", 20)), int(os.environ.get("PER", 150))
 for v in variants + variants:
     ops.lib.dw_debug_set(0, v)
@@ -30,4 +30,4 @@ for v in variants + variants:
         torch.cuda.synchronize()
         tf = [2.0 * M * N * K * per / (ev[c].elapsed_time(ev[c + 1]) * 1e-3) / 1e12 for c in range(chunks)]
         print(f"vendor    N={N} K={K}: " + " ".join(f"{x:.0f}" for x in tf), flush=True)
-ops.lib.dw_debug_set(0, 2163)
+ops.lib.dw_debug_set(0, 0)
