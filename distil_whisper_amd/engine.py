@@ -31,6 +31,7 @@ class WhisperDims:
     max_tgt: int = 448
     pad_token_id: int = 50256
     decoder_start_token_id: int = 50257
+    median_filter_width: int = 7     # token-level timestamps (TF:generation_whisper.py:346; on the model config in the reference)
 
     @staticmethod
     def from_any(c):
@@ -40,9 +41,10 @@ class WhisperDims:
         if hasattr(c, "encoder_attention_heads"):
             return WhisperDims(c.d_model, c.encoder_attention_heads, c.encoder_ffn_dim, c.encoder_layers,
                                c.decoder_layers, c.vocab_size, c.num_mel_bins, c.max_source_positions,
-                               c.max_target_positions, c.pad_token_id, c.decoder_start_token_id)
+                               c.max_target_positions, c.pad_token_id, c.decoder_start_token_id,
+                               getattr(c, "median_filter_width", 7))
         return WhisperDims(c.d_model, c.heads, c.ffn, c.enc_layers, c.dec_layers, c.vocab, c.n_mels, c.max_src,
-                           c.max_tgt, c.pad_token_id, c.decoder_start_token_id)
+                           c.max_tgt, c.pad_token_id, c.decoder_start_token_id, getattr(c, "median_filter_width", 7))
 
 
 def _rup(x, m):
@@ -497,12 +499,14 @@ class WhisperEngine:
             ctx.update(x_final=x, mu=mu, rs=rs, enc_out=y)
         return y, ctx
 
-    def _layer_fwd(self, p, x, B, L, enc_out, Lk, causal, save, Rg=None, live=None):
+    def _layer_fwd(self, p, x, B, L, enc_out, Lk, causal, save, Rg=None, live=None, probe=None):
         """One pre-LN transformer layer (TF:modeling_whisper.py:379-413 encoder, 448-505 decoder).  Rg >= the valid
         rows: rows the projections run over (`pad_gemm_rows`; x then has Rg rows); attention and LayerNorm see the valid
         rows.  live (forward-only passes): x holds the packed live rows (LiveRows); attention runs in the (batch,
         position) layout between a scatter and a gather -- its dead rows hold stale memory, which only ever reaches
-        dead rows (queries are independent, the causal mask hides later keys, encoder keys are all live)."""
+        dead rows (queries are independent, the causal mask hides later keys, encoder keys are all live).
+        probe (off by default; alignment_probs): (heads int32 on the device, probs, slot0) -- the cross-attention probabilities of
+        the listed heads of this layer are written to probs[:, slot0:slot0 + len(heads)] from the q / k the layer projects."""
         ops, st, d = self.ops, self.st, self.dims
         D, H, Rp = d.d_model, d.heads, B * L
         R = Rp if live is None else live.n          # valid rows of x
@@ -576,6 +580,9 @@ class WhisperEngine:
             ops.gemm(h[:Rg], cv["wqkv"][:D], bias=cv["bqkv"][:D], out=q[:Rg])
             kv = self.act(Re, 2 * D, zero_pad=save, pad=self.row_pad)
             ops.gemm(enc_out[:Re], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=kv[:Re])
+            if probe is not None:
+                assert live is None
+                ops.cross_attn_probs(q[:R], kv[:Re, :D], probe[0], probe[1], probe[2], B, L, Lk)
             o, lse = attend(q, kv[:Re, :D], kv[:Re, D:], Lk, False, D)
             x1 = ops.gemm(o[:Rg], cv["wo"], bias=cv["bo"], residual=x, round_res=True, out_dtype=self.stream, out_row_pad=xp)
             if save:
@@ -662,6 +669,36 @@ class WhisperEngine:
         if save:
             ctx.update(x_final=x, mu=mu, rs=rs, hf=hf, lm_rows=Rl, live=live, packed=packed, Rv=Rv)
         return logits, ctx
+
+    def alignment_probs(self, ids, enc_out, alignment_heads):
+        """Cross-attention probabilities of the `(layer, head)` pairs of `alignment_heads` over the token ids [B, L]: one
+        forward-only, teacher-forced decoder pass (no LM head) -> f32 [B, len(alignment_heads), L, ldp], head slots in the order of
+        the list, max_src valid columns.  What the reference gathers step by step from `output_attentions` (TF:generation_whisper.py:
+        252-261) as one function of the same token prefix -- the way the original Whisper implementation computes it; the graph-
+        captured token step stays as it is."""
+        ops, st, d = self.ops, self.st, self.dims
+        B, L = ids.shape
+        pairs = [(int(l), int(h)) for l, h in alignment_heads]
+        for l, h in pairs:
+            if not (0 <= l < d.dec_layers and 0 <= h < d.heads):
+                raise ValueError(f"alignment head {(l, h)} outside the decoder's {d.dec_layers} layers x {d.heads} heads")
+        # one kernel launch per layer, filling the consecutive head slots of that layer's pairs
+        runs = {}
+        for i, (l, h) in enumerate(pairs):
+            if l in runs and pairs[i - 1][0] != l:
+                raise ValueError(f"alignment_heads must be grouped by layer (as every Whisper generation config lists them): {pairs}")
+            runs.setdefault(l, [i, []])[1].append(h)
+        probs = ops.empty((B, len(pairs), L, _rup(d.max_src, 4)), torch.float32)
+        tabs = st.p if self.stream == torch.float32 else st.s
+        x = ops.embed_fwd(ids.contiguous(), tabs["model.decoder.embed_tokens.weight"],
+                          tabs["model.decoder.embed_positions.weight"], self.stream)
+        for layer in range(max(runs) + 1):
+            probe = None
+            if layer in runs:
+                slot0, heads = runs[layer]
+                probe = (torch.tensor(heads, dtype=torch.int32, device=ids.device), probs, slot0)
+            x, _ = self._layer_fwd(f"model.decoder.layers.{layer}", x, B, L, enc_out, d.max_src, True, False, probe=probe)
+        return probs
 
     # ---- incremental decoding with a KV cache (TF:modeling_whisper.py:312-335, EncoderDecoderCache) -----------------
     def decode_init(self, enc_out, B, max_len, cache=None):

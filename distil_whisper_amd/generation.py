@@ -11,6 +11,8 @@ Reference behaviour (the arithmetic lives in the third-party `transformers` pack
     <|notimestamps|> unless timestamps are requested), TF:1853-1918 `_prepare_decoder_input_ids` (prompt_ids in front);
   * lengths: TF:1920-1947 `_set_max_new_tokens_and_length`;
   * logits processors and their order: TF:1774-1812 (begin-suppress, suppress, timestamp rules);
+  * token-level timestamps (`return_token_timestamps=True`, TF:241-381, 1146-1157, 1685-1700): alignment.py + csrc/align.hip;
+    the generation config carries `alignment_heads` ([[layer, head], ...]), the model config `median_filter_width`;
   * return value: without `return_dict_in_generate` the generated tokens only (decoder prompt and EOS stripped,
     right-padded with pad_token_id, TF:913-957 + `_pad_to_max_length`); with it an object whose `.sequences` holds
     prompt + generated tokens as GenerationMixin returns them.
@@ -46,7 +48,7 @@ _CONFIG_KEYS = ("max_length", "max_new_tokens", "min_new_tokens", "num_beams", "
                 "lang_to_id", "task_to_id", "is_multilingual", "return_timestamps", "language", "task",
                 "forced_decoder_ids", "num_return_sequences", "use_cache", "output_scores", "return_dict_in_generate",
                 "num_assistant_tokens", "prompt_condition_type", "length_penalty", "repetition_penalty",
-                "no_repeat_ngram_size", "temperature", "early_stopping", "num_beam_groups")
+                "no_repeat_ngram_size", "temperature", "early_stopping", "num_beam_groups", "alignment_heads")
 
 
 class GenerationConfig:
@@ -113,15 +115,19 @@ class GenerationConfig:
 class GenerateOutput:
     """`return_dict_in_generate=True` result: .sequences int64 [B, prompt + generated] (GenerateEncoderDecoderOutput)."""
 
-    def __init__(self, sequences, scores=None):
+    def __init__(self, sequences, scores=None, token_timestamps=None, segments=None):
         self.sequences = sequences
         self.scores = scores
+        if token_timestamps is not None:       # return_token_timestamps=True: float32 seconds per token of `sequences`
+            self.token_timestamps = token_timestamps
+        if segments is not None:
+            self.segments = segments
 
     def __getitem__(self, k):
         return getattr(self, k)
 
     def keys(self):
-        return [k for k in ("sequences", "scores") if getattr(self, k) is not None]
+        return [k for k in ("sequences", "scores", "token_timestamps", "segments") if getattr(self, k, None) is not None]
 
 
 def language_to_id(language, gc):
@@ -260,9 +266,11 @@ def resolve_lengths(gc, prompt_len, max_target_positions, explicit_max_length):
     return int(mnt), int(min(mn, mnt))
 
 
-def strip_and_pad(sequences, prompt_len, eos_token_id, pad_token_id):
+def strip_and_pad(sequences, prompt_len, eos_token_id, pad_token_id, token_timestamps=None):
     """The plain return value of the reference's `generate` (TF:1060-1093 + `_pad_to_max_length`): per row the tokens
-    after the decoder prompt, with trailing pads and the final EOS removed, right-padded to the longest row."""
+    after the decoder prompt, with trailing pads and the final EOS removed, right-padded to the longest row.
+    token_timestamps (float32 [B, seq_len], return_token_timestamps=True): -> (tokens, the kept tokens' times, each row
+    right-padded with its last value, TF:188-229)."""
     rows = []
     for row in sequences.tolist():
         seq = row[prompt_len:]
@@ -281,14 +289,22 @@ def strip_and_pad(sequences, prompt_len, eos_token_id, pad_token_id):
     for i, r in enumerate(rows):
         if r:
             out[i, : len(r)] = torch.as_tensor(r, dtype=torch.long, device=sequences.device)
+    if token_timestamps is not None:
+        ts = torch.zeros((len(rows), width), dtype=token_timestamps.dtype, device=token_timestamps.device)
+        for i, r in enumerate(rows):
+            if r:
+                ts[i, : len(r)] = token_timestamps[i, prompt_len:prompt_len + len(r)]
+                ts[i, len(r):] = ts[i, len(r) - 1]
+        return out, ts
     return out
 
 
 def retrieve_segment(seq, timestamp_begin, seek_num_frames, time_offset=0.0, time_precision=0.02,
-                     time_precision_features=0.01, input_stride=2):
+                     time_precision_features=0.01, input_stride=2, with_idxs=False):
     """`WhisperGenerationMixin._retrieve_segment` (TF:generation_whisper.py:1977-2075) on a list of token ids: split the
     tokens generated for one window at consecutive timestamp pairs ("end of segment" predictions) and say how many mel
-    frames the window consumed.  -> (segments [{"start", "end", "tokens"}], segment_offset in frames)."""
+    frames the window consumed.  -> (segments [{"start", "end", "tokens"}], segment_offset in frames).  with_idxs: every
+    segment also says which slice of `seq` it is ("idxs", without the reference's decoder-prompt offset)."""
     n = len(seq)
     ts = [t >= timestamp_begin for t in seq]
     single_ending = ts[-2:] == [False, True]
@@ -306,6 +322,8 @@ def retrieve_segment(seq, timestamp_begin, seek_num_frames, time_offset=0.0, tim
             end_tok = sl[-1] if (not is_last or single_ending) else sl[-2]
             segments.append({"start": time_offset + (sl[0] - timestamp_begin) * time_precision,
                              "end": time_offset + (end_tok - timestamp_begin) * time_precision, "tokens": sl})
+            if with_idxs:
+                segments[-1]["idxs"] = (last, cur)
             last = cur
         if single_ending:
             offset = int(seek_num_frames)          # a single timestamp at the end: no speech after it
@@ -316,5 +334,7 @@ def retrieve_segment(seq, timestamp_begin, seek_num_frames, time_offset=0.0, tim
     last_pos = int(seek_num_frames * time_precision_features / time_precision)
     if stamps and stamps[-1] != timestamp_begin:
         last_pos = stamps[-1] - timestamp_begin
-    return [{"start": time_offset, "end": time_offset + last_pos * time_precision, "tokens": list(seq)}], \
-        int(seek_num_frames)
+    seg = {"start": time_offset, "end": time_offset + last_pos * time_precision, "tokens": list(seq)}
+    if with_idxs:
+        seg["idxs"] = (0, n)
+    return [seg], int(seek_num_frames)

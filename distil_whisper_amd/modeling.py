@@ -760,8 +760,12 @@ class WhisperForConditionalGeneration(nn.Module):
         sampling (a positive `temperature`, as in the reference's generate_with_fallback, with `top_k` / `top_p`):
         decoding.GreedyDecoder `soft` -- token for token the reference's on the same device and seed.
         Arguments this path does not implement RAISE (nothing is silently ignored): group beam search, those three options
-        combined with beams / an assistant / the seek loop, the fallback heuristics outside the seek loop, token-level
-        timestamps, custom logits processors.
+        combined with beams / an assistant / the seek loop, the fallback heuristics outside the seek loop, custom logits
+        processors, `return_token_timestamps` combined with beams / an assistant / sampling / the fallback heuristics.
+        `return_token_timestamps=True` (greedy; single window and the seek loop; TF:241-381): one more decoder pass over the
+        finished sequences and three kernels (alignment.extract_token_timestamps) -- the result is a dict {"sequences",
+        "token_timestamps"[, "segments"]} as in the reference (TF:941-968); `attention_mask` gives the valid frames per row;
+        `alignment_heads=[[layer, head], ...]` may be passed like any other generation-config field.
         Returns what the reference returns: the generated tokens only (decoder prompt and EOS stripped, right-padded
         with pad_token_id), or with `return_dict_in_generate=True` / `force_unique_generate_call=True` the full
         sequences (prompt + generated, as GenerationMixin emits them)."""
@@ -773,8 +777,6 @@ class WhisperForConditionalGeneration(nn.Module):
                           ("prefix_allowed_tokens_fn", prefix_allowed_tokens_fn), ("monitor_progress", monitor_progress)):
             if val is not None and (not hasattr(val, "__len__") or len(val) > 0):
                 raise NotImplementedError(f"generate({name}=...) is not implemented on the MI355X engine path")
-        if return_token_timestamps:
-            raise NotImplementedError("return_token_timestamps is not implemented on the MI355X path")
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
         fallback_args = dict(temperatures=temps, compression_ratio_threshold=compression_ratio_threshold,
                              logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold,
@@ -814,6 +816,27 @@ class WhisperForConditionalGeneration(nn.Module):
                                           "single-window decoding with the KV cache (not with beams, an assistant or use_cache=False)")
         if gc.decoder_start_token_id is None:
             gc.decoder_start_token_id = d.decoder_start_token_id
+        # ---- token-level timestamps (TF:1685-1700 `_set_num_frames`): what the alignment pass needs, or a loud refusal
+        token_ts = None
+        if return_token_timestamps:
+            from . import alignment as A
+            if task == "translate" or (task is None and getattr(gc, "task", None) == "translate"):
+                A.logger.warning(A.TRANSLATE_WARNING)
+            if not hasattr(gc, "alignment_heads"):
+                raise A.TokenTimestampsUnavailable(A.NO_ALIGNMENT_HEADS)
+            A.check_filter_width(int(d.median_filter_width))
+            if num_beams > 1 or kwargs.get("assistant_model") is not None or sample_temp is not None or uses_fallback:
+                raise NotImplementedError(
+                    "return_token_timestamps is implemented for greedy decoding (single window and the timestamp seek loop); "
+                    "combined with beam search, an assistant_model, sampling or the temperature-fallback / "
+                    "condition_on_prev_tokens heuristics it is not implemented on the MI355X path")
+            if attention_mask is not None:
+                nf = [int(x) for x in attention_mask.sum(-1).tolist()]
+            else:
+                A.warn_once(A.NO_ATTENTION_MASK)
+                nf = None
+            token_ts = dict(alignment_heads=[list(x) for x in gc.alignment_heads], num_frames=nf,
+                            time_precision=time_precision)
         # ---- encoder
         encoder_outputs = kwargs.get("encoder_outputs")
         if encoder_outputs is not None:
@@ -850,7 +873,7 @@ class WhisperForConditionalGeneration(nn.Module):
                                               "single-window decoding, not inside the timestamp seek loop, on the MI355X path")
                 return self._generate_seek_loop(input_features, attention_mask, gc, language, task, is_multilingual,
                                                 prompt_ids, kwargs, use_graphs, return_dict_in_generate, num_beams,
-                                                fallback_args, return_segments)
+                                                fallback_args, return_segments, token_ts)
             if return_segments:
                 raise NotImplementedError("return_segments comes with the timestamp seek loop (return_timestamps=True) "
                                           "on the MI355X path")
@@ -968,6 +991,17 @@ class WhisperForConditionalGeneration(nn.Module):
                 raise ValueError("return_timestamps=True runs on the KV-cache decoder (use_cache=True)")
             seqs = self._greedy_no_cache(enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress)
         seqs = self._trim_finished(seqs, P, eos, pad)
+        if token_ts is not None:
+            # TF:1146-1157: one alignment pass over the finished sequences; which shape comes back: TF:913-968
+            from .alignment import extract_token_timestamps
+            ts = extract_token_timestamps(self, seqs, enc, token_ts["alignment_heads"], token_ts["num_frames"], P,
+                                          token_ts["time_precision"])
+            if return_dict_in_generate or getattr(gc, "return_dict_in_generate", False):
+                return G.GenerateOutput(seqs, token_timestamps=ts)
+            if force_unique_generate_call:
+                return {"sequences": seqs, "token_timestamps": ts}
+            plain, plain_ts = G.strip_and_pad(seqs, P, eos, pad, token_timestamps=ts)
+            return {"sequences": plain, "token_timestamps": plain_ts}
         if return_dict_in_generate or getattr(gc, "return_dict_in_generate", False):
             return G.GenerateOutput(seqs)
         if force_unique_generate_call:
@@ -979,7 +1013,7 @@ class WhisperForConditionalGeneration(nn.Module):
                     detect_language=None, temperatures=(0.0,), compression_ratio_threshold=None, logprob_threshold=None,
                     no_speech_threshold=None, condition_on_prev_tokens=False, prev_sot_token_id=None, prompt_ids=None,
                     prompt_all_segments=False, num_beams=1, length_penalty=1.0, early_stopping=False, assistant=None,
-                    num_assistant_tokens=5):
+                    num_assistant_tokens=5, token_timestamps=None):
         """The seek loop itself (TF:generation_whisper.py:784-903): input_features [B, n_mels, frames], max_frames[b] =
         valid mel frames of utterance b.  init_tokens: the decoder prompt rows (list of B lists) or a callable(detect)
         building them (detect() = language ids from the first window); lengths(P) -> (max_new_tokens, min_new_tokens)
@@ -1005,6 +1039,10 @@ class WhisperForConditionalGeneration(nn.Module):
           * assistant = (engine, encode) of a draft model (run_eval.py:578-599, 706-707 with long-form inputs): the
             temperature-0 pass of a window is decoding.assisted_greedy_decode with the timestamp rules; encode(features)
             gives the assistant's encoder output of a window batch, or None when it shares this model's.
+          * token_timestamps = dict(alignment_heads, num_frames, time_precision) (greedy passes only): every window's finished
+            batch goes through alignment.extract_token_timestamps with `num_frames - seek` of its rows (TF:1146-1157); a segment
+            then carries "token_timestamps" (its tokens' times plus the window's offset, TF:2034-2036, 2068-2070) and, as in the
+            reference, "result" = {"token_timestamps": the window's row} with "idxs" = the segment's slice of it.
         -> per utterance the list of segments {"start", "end", "tokens"}."""
         import math
         import zlib
@@ -1042,6 +1080,9 @@ class WhisperForConditionalGeneration(nn.Module):
                                       "MI355X path (the reference scores beams by `sequences_scores`)")
         if no_speech_threshold is not None and logprob_threshold is None:
             raise ValueError("no_speech_threshold needs logprob_threshold (the reference compares both)")
+        if token_timestamps is not None and (any(t > 0.0 for t in temps) or assistant is not None or int(num_beams) > 1):
+            raise NotImplementedError("token timestamps in the seek loop are implemented for greedy passes (no sampled fallback, "
+                                      "assistant or beams) on the MI355X path")
 
         def vmask(ids):
             mk = torch.zeros(V, dtype=torch.bool, device=dev)
@@ -1148,7 +1189,7 @@ class WhisperForConditionalGeneration(nn.Module):
                 elif prompt:
                     pre = list(prompt)
                 prompts[b] = pre + list(init[b])
-            accepted = {}
+            accepted, window_ts = {}, {}
             # (the reference left-pads the batch to its longest prompt and derives the lengths from that, TF:835-840)
             max_new, min_new = lengths(max(len(prompts[b]) for b in rows))
             for P in sorted({len(prompts[b]) for b in rows}):
@@ -1194,7 +1235,17 @@ class WhisperForConditionalGeneration(nn.Module):
                                 check_every=4,      # eager passes: stop within 3 steps of the last row's EOS
                                 timestamp_rules=dict(begin_index=P, no_timestamps_token_id=nts,
                                                      max_initial_timestamp_index=max_initial_timestamp_index))
-                        out = dec.run(enc, ids, max_new, min_new)[:, P:].tolist()
+                        full = dec.run(enc, ids, max_new, min_new)
+                        if token_timestamps is not None:
+                            from .alignment import extract_token_timestamps
+                            nf = token_timestamps["num_frames"]
+                            ts = extract_token_timestamps(
+                                self, self._trim_finished(full, P, eos, pad), enc, token_timestamps["alignment_heads"],
+                                None if nf is None else [nf[b] - seek[b] for b in pending], P,
+                                token_timestamps["time_precision"]).cpu()
+                            for i, b in enumerate(pending):
+                                window_ts[b] = ts[i]
+                        out = full[:, P:].tolist()
                     gens = []
                     for seq in out:
                         if seq and seq[-1] == pad:     # TF:1064-1071: drop the padding (all but one EOS when pad == EOS)
@@ -1228,13 +1279,24 @@ class WhisperForConditionalGeneration(nn.Module):
                 if skip:
                     seek[b] += snf[b]
                     continue
-                segs, offset = G.retrieve_segment(seq, tb, snf[b], time_offset=seek[b] * 0.01)
+                segs, offset = G.retrieve_segment(seq, tb, snf[b], time_offset=seek[b] * 0.01,
+                                                  with_idxs=token_timestamps is not None)
+                if token_timestamps is not None:
+                    P = len(prompts[b])
+                    # TF:800-802: the window's offset in seconds, a double; added to the float32 row as the reference adds it
+                    t_off = torch.tensor(seek[b], dtype=torch.float64) * token_timestamps["time_precision"] / 2
+                    for sg in segs:
+                        i0, i1 = sg["idxs"]
+                        sg["idxs"] = (P + i0, P + i1)
+                        sg["result"] = {"token_timestamps": window_ts[b]}
+                        sg["token_timestamps"] = window_ts[b][P + i0:P + i1] + t_off
                 seek[b] += offset
                 segments[b] += segs
         return [sg[1:] for sg in segments] if first_segment_prompt else segments
 
     def _generate_seek_loop(self, input_features, attention_mask, gc, language, task, is_multilingual, prompt_ids, kwargs,
-                            use_graphs, return_dict_in_generate, num_beams, fallback_args=None, return_segments=False):
+                            use_graphs, return_dict_in_generate, num_beams, fallback_args=None, return_segments=False,
+                            token_ts=None):
         """Timestamp-driven multi-pass transcription: `WhisperGenerationMixin.generate` steps 5-7 (TF:745-968) with
         temperature 0 and no fallback thresholds -- every utterance keeps a `seek` position in mel frames; each pass
         decodes the next <= 30 s window of every unfinished utterance with the timestamp rules, `retrieve_segment`
@@ -1314,13 +1376,29 @@ class WhisperForConditionalGeneration(nn.Module):
                                         getattr(am, "generation_config", None), "num_assistant_tokens", None) or 5),
                                     length_penalty=1.0 if getattr(gc, "length_penalty", None) is None else gc.length_penalty,
                                     early_stopping=getattr(gc, "early_stopping", False) or False,
-                                    **(fallback_args or {}))
+                                    token_timestamps=token_ts, **(fallback_args or {}))
         rows_out = [[tok for sg in segments[b] for tok in sg["tokens"]] for b in range(B)]
         width = max((len(r) for r in rows_out), default=0)
         seqs = torch.full((B, width), pad, dtype=torch.long, device=dev)
         for b, r in enumerate(rows_out):
             if r:
                 seqs[b, :len(r)] = torch.as_tensor(r, dtype=torch.long, device=dev)
+        if token_ts is not None:
+            # `_pad_to_max_length` (TF:150-235): per utterance the windows' own values of its segments' tokens (without the time
+            # offsets, as the reference concatenates them), right-padded with the row's last value
+            rows_ts = [[sg["result"]["token_timestamps"][sg["idxs"][0]:sg["idxs"][1]] for sg in segments[b]] for b in range(B)]
+            ts = torch.zeros((B, width), dtype=torch.float32)
+            for b, parts in enumerate(rows_ts):
+                if parts:
+                    row = torch.cat(parts, -1)
+                    ts[b, :len(row)] = row
+                    if len(row):
+                        ts[b, len(row):] = row[-1]
+            out = {"sequences": seqs, "token_timestamps": ts.to(dev)}
+            rdig = return_dict_in_generate or getattr(gc, "return_dict_in_generate", False)
+            if return_segments or rdig:          # TF:945-949: return_dict_in_generate switches return_segments on
+                out["segments"] = segments
+            return G.GenerateOutput(seqs, token_timestamps=out["token_timestamps"], segments=segments) if rdig else out
         if return_segments:
             return {"sequences": seqs, "segments": segments}
         if return_dict_in_generate or getattr(gc, "return_dict_in_generate", False):

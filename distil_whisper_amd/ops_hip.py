@@ -99,6 +99,12 @@ _SIGS = {
     "dw_greedy_select": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                          [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                           C.c_void_p], C.c_int),
+    "dw_cross_attn_probs": ([C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int64,
+                                                                                                    C.c_float, C.c_void_p], C.c_int),
+    "dw_align_prepare": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                          C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "dw_dtw": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                C.c_void_p], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
@@ -128,6 +134,10 @@ def _dt(t):
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def _rup4(x):
+    return (int(x) + 3) // 4 * 4
 
 
 class HipOps:
@@ -610,6 +620,51 @@ class HipOps:
                                             int(begin_index), int(eos), int(fill), _p(done), _p(cur), self._stream()),
                   "greedy_select")
 
+    # ---- token-level timestamps (csrc/align.hip; TF:generation_whisper.py:241-381) ------------------------------------
+    def cross_attn_probs(self, q, k, heads, probs, slot0, B, L, Lk, kv_batch_rows=None, scale=0.125):
+        """probs[:, slot0:slot0 + len(heads), :, :Lk] = softmax(scale * q k^T) of the listed heads (int32, on the device).
+        q [>= B*L, H*64], k [>= B*kv_batch_rows, H*64] bf16 with unit column stride; probs f32 [B, n_total, L, ldp] contiguous."""
+        assert q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and q.stride(1) == 1 and k.stride(1) == 1
+        assert heads.dtype == torch.int32 and heads.is_contiguous() and heads.device == q.device
+        assert probs.dtype == torch.float32 and probs.is_contiguous() and probs.dim() == 4
+        assert probs.shape[0] == B and probs.shape[2] == L and q.shape[0] >= B * L and q.shape[1] == k.shape[1]
+        rows = Lk if kv_batch_rows is None else int(kv_batch_rows)
+        assert k.shape[0] >= (B - 1) * rows + Lk
+        self._chk(self.lib.dw_cross_attn_probs(_p(q), _p(k), _p(heads), heads.numel(), _p(probs), B, q.shape[1] // 64, L, int(Lk),
+                                               q.stride(0), k.stride(0), rows, probs.shape[1], int(slot0), probs.shape[3],
+                                               float(scale), self._stream()), "cross_attn_probs")
+        return probs
+
+    def align_prepare(self, probs, n_tok, n_frames, first_tok, max_frames, width, cost=None):
+        """Normalise over tokens, median-filter over frames, average the heads, negate: probs f32 [B, n, L, ldp] -> cost f32
+        [B, L, ldc] (rows 0 .. n_tok[b] - 1, columns 0 .. n_frames[b] - 1 of row b are written).  n_tok / n_frames: int32 [B]."""
+        B, n, L, ldp = probs.shape
+        assert probs.dtype == torch.float32 and probs.is_contiguous()
+        if cost is None:
+            cost = self.empty((B, L, _rup4(max_frames)), torch.float32)
+        assert cost.dtype == torch.float32 and cost.is_contiguous() and cost.shape[:2] == (B, L)
+        for t in (n_tok, n_frames):
+            assert t.dtype == torch.int32 and t.numel() == B and t.is_contiguous() and t.device == probs.device
+        self._chk(self.lib.dw_align_prepare(_p(probs), B, n, L, ldp, int(first_tok), _p(n_tok), _p(n_frames), int(max_frames),
+                                            int(width), _p(cost), cost.shape[2], self._stream()), "align_prepare")
+        return cost
+
+    def dtw(self, cost, n_tok, n_frames, max_frames, first_frame=None):
+        """Dynamic time warping + backtrace per batch row: cost f32 [B, L, ldc] -> first_frame int32 [B, L] (entries behind
+        n_tok[b] keep what they held: zeros when allocated here)."""
+        B, L, ldc = cost.shape
+        assert cost.dtype == torch.float32 and cost.is_contiguous()
+        for t in (n_tok, n_frames):
+            assert t.dtype == torch.int32 and t.numel() == B and t.is_contiguous() and t.device == cost.device
+        if first_frame is None:
+            first_frame = self.zeros((B, L), torch.int32)
+        assert first_frame.dtype == torch.int32 and first_frame.is_contiguous() and first_frame.shape == (B, L)
+        tld = (int(max_frames) + 15) // 16
+        trace = self.empty((B, L, tld), torch.int32)         # scratch: two bits per cell of the table
+        self._chk(self.lib.dw_dtw(_p(cost), B, L, ldc, _p(n_tok), _p(n_frames), int(max_frames), _p(trace), tld, _p(first_frame),
+                                  self._stream()), "dtw")
+        return first_frame
+
     def adamw(self, p, g, m, v, shadow, sumsq, max_norm, grad_mul, lr, beta1, beta2, eps, weight_decay, step):
         assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
         self._chk(self.lib.dw_adamw(_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), _p(sumsq), float(max_norm),
@@ -647,5 +702,6 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("logmel", "logmel"), ("adamw", "adamw"), ("adamw_dev", "adamw"), ("cast_bf16", "cast"), ("colsum", "colsum"),
                     ("sumsq", "sumsq"), ("embed_fwd", "embed"), ("embed_bwd", "embed"), ("im2col_mel", "conv_aux"),
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),
-                    ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select")):
+                    ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("cross_attn_probs", "align"),
+                    ("align_prepare", "align"), ("dtw", "align")):
     setattr(HipOps, _name, _timed(_key)(getattr(HipOps, _name)))

@@ -303,6 +303,35 @@ typedef struct DwDecodeStep {
 } DwDecodeStep;
 int dw_decode_step(const DwDecodeStep* d, void* stream);
 
+/* ---- token-level timestamps (TF:generation_whisper.py:241-381 `_extract_token_timestamps`, :43-61 `_median_filter`, :64-115
+ * `_dynamic_time_warping`; reached from `generate(return_token_timestamps=True)`, TF:1146-1157).  The reference collects every
+ * decoding step's eager cross-attention matrix and post-processes it on the host; here one teacher-forced decoder pass hands
+ * the alignment layers' q / k projections to the first entry point and the rest stays on the device.
+ *
+ * dw_cross_attn_probs: probs[b][slot0 + i][l][0 .. Lk) = softmax over the Lk keys of scale * q[b*L + l, head heads[i]] .
+ * k[b*kv_batch_rows + key, head heads[i]], i < n.  q bf16 [B*L rows][ldq], k bf16 [B][kv_batch_rows][ldk] (head h of a row at
+ * element offset h*64; H = heads per row), heads int32 [n] ON THE DEVICE (an id outside [0, H) leaves its slot untouched),
+ * probs f32 [B][n_total][L][ldp] -- the layers of one model fill one tensor, slot by slot.  fp32 softmax with the exact row
+ * maximum.  ldq / ldk multiples of 8, ldp a multiple of 4 and >= Lk, 16-byte aligned bases, L <= 512, n_total <= 32. */
+int dw_cross_attn_probs(const void* q, const void* k, const int32_t* heads, int n, float* probs, int B, int H, int L, int Lk,
+                        int64_t ldq, int64_t ldk, int64_t kv_batch_rows, int n_total, int slot0, int64_t ldp, float scale,
+                        void* stream);
+/* dw_align_prepare (TF:341-365): for batch row b the token rows first_tok .. first_tok + n_tok[b] - 1 and the frame columns
+ * 0 .. n_frames[b] - 1 of probs [B][n_heads][L][ldp] (n_tok / n_frames: int32 [B] on the device, clamped to L - first_tok /
+ * max_frames): per (head, frame) column (w - mean) / std over the token axis (population std; a zero spread divides as IEEE
+ * does), median of median_filter_width (odd, 1..9) along the frames with reflect padding -- unfiltered when n_frames[b] <=
+ * width / 2 --, mean over the heads, negated -> cost f32 [B][L][ldc], rows 0 .. n_tok[b] - 1. */
+int dw_align_prepare(const float* probs, int B, int n_heads, int L, int64_t ldp, int first_tok, const int32_t* n_tok,
+                     const int32_t* n_frames, int max_frames, int median_filter_width, float* cost, int64_t ldc, void* stream);
+/* dw_dtw (TF:64-115, 367-369): dynamic time warping over cost[b] (n_tok[b] x n_frames[b]) and its backtrace, one workgroup per
+ * batch row -> first_frame int32 [B][L]: the frame index at which the path first reaches each token (`time_indices[jumps]`;
+ * -1 where the reference's path reaches the token in its border column).  Same path as the reference function: one fp32
+ * addition per cell, the same strict comparisons (ties, inf and NaN choose "left").  trace: caller-owned scratch, uint32
+ * [B][L][trace_ld] with trace_ld >= ceil(max_frames / 16) (two bits per cell).  Rows with n_tok[b] == 0 and the entries behind
+ * n_tok[b] are left as they are.  L <= 512. */
+int dw_dtw(const float* cost, int B, int L, int64_t ldc, const int32_t* n_tok, const int32_t* n_frames, int max_frames,
+           uint32_t* trace, int64_t trace_ld, int32_t* first_frame, void* stream);
+
 /* ---- self tests (diagnostics for bring-up; not on the hot path) --------------------------------------------------
  * Runs ds_read_b64_tr_b16 on a known LDS image: out int32 [64][4] = element ids received by each lane. */
 int dw_selftest_tr16(int32_t* out, void* stream);
