@@ -13,6 +13,8 @@ Reference behaviour (the arithmetic lives in the third-party `transformers` pack
   * logits processors and their order: TF:1774-1812 (begin-suppress, suppress, timestamp rules);
   * token-level timestamps (`return_token_timestamps=True`, TF:241-381, 1146-1157, 1685-1700): alignment.py + csrc/align.hip;
     the generation config carries `alignment_heads` ([[layer, head], ...]), the model config `median_filter_width`;
+  * per-step scores (`output_scores` / `output_logits` with `return_dict_in_generate`, TF:generation/utils.py `_sample`;
+    `compute_transition_scores`): scoring.py + csrc/score.hip;
   * return value: without `return_dict_in_generate` the generated tokens only (decoder prompt and EOS stripped,
     right-padded with pad_token_id, TF:913-957 + `_pad_to_max_length`); with it an object whose `.sequences` holds
     prompt + generated tokens as GenerationMixin returns them.
@@ -46,7 +48,8 @@ _CONFIG_KEYS = ("max_length", "max_new_tokens", "min_new_tokens", "num_beams", "
                 "eos_token_id", "pad_token_id", "bos_token_id", "decoder_start_token_id", "suppress_tokens",
                 "begin_suppress_tokens", "no_timestamps_token_id", "max_initial_timestamp_index", "prev_sot_token_id",
                 "lang_to_id", "task_to_id", "is_multilingual", "return_timestamps", "language", "task",
-                "forced_decoder_ids", "num_return_sequences", "use_cache", "output_scores", "return_dict_in_generate",
+                "forced_decoder_ids", "num_return_sequences", "use_cache", "output_scores", "output_logits",
+                "return_dict_in_generate",
                 "num_assistant_tokens", "prompt_condition_type", "length_penalty", "repetition_penalty",
                 "no_repeat_ngram_size", "temperature", "early_stopping", "num_beam_groups", "alignment_heads")
 
@@ -113,11 +116,13 @@ class GenerationConfig:
 
 
 class GenerateOutput:
-    """`return_dict_in_generate=True` result: .sequences int64 [B, prompt + generated] (GenerateEncoderDecoderOutput)."""
+    """`return_dict_in_generate=True` result: .sequences int64 [B, prompt + generated] (GenerateEncoderDecoderOutput);
+    .scores / .logits (output_scores / output_logits, else None): scoring.StepScores, one f32 [B, vocab] tensor per generated step."""
 
-    def __init__(self, sequences, scores=None, token_timestamps=None, segments=None):
+    def __init__(self, sequences, scores=None, token_timestamps=None, segments=None, logits=None):
         self.sequences = sequences
         self.scores = scores
+        self.logits = logits
         if token_timestamps is not None:       # return_token_timestamps=True: float32 seconds per token of `sequences`
             self.token_timestamps = token_timestamps
         if segments is not None:
@@ -127,7 +132,7 @@ class GenerateOutput:
         return getattr(self, k)
 
     def keys(self):
-        return [k for k in ("sequences", "scores", "token_timestamps", "segments") if getattr(self, k, None) is not None]
+        return [k for k in ("sequences", "scores", "logits", "token_timestamps", "segments") if getattr(self, k, None) is not None]
 
 
 def language_to_id(language, gc):

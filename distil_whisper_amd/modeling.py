@@ -762,6 +762,13 @@ class WhisperForConditionalGeneration(nn.Module):
         Arguments this path does not implement RAISE (nothing is silently ignored): group beam search, those three options
         combined with beams / an assistant / the seek loop, the fallback heuristics outside the seek loop, custom logits
         processors, `return_token_timestamps` combined with beams / an assistant / sampling / the fallback heuristics.
+        `output_scores=True` / `output_logits=True` with `return_dict_in_generate=True` (single-window greedy search, with or
+        without the KV cache, HIP graphs, prompt_ids / decoder_input_ids / encoder_outputs, the timestamp rules under
+        `force_unique_generate_call`, together with `return_token_timestamps`): `.scores` / `.logits` hold one f32 [batch, vocab]
+        tensor per generated step as in GenerationMixin, computed by one more teacher-forced decoder pass and csrc/score.hip
+        (scoring.py; a near tie may therefore rank another token first than the token step did).  Combined with beam search,
+        an assistant_model, sampling / repetition_penalty / no_repeat_ngram_size or the timestamp seek loop they RAISE; without
+        `return_dict_in_generate` they change nothing (the reference drops them there too).
         `return_token_timestamps=True` (greedy; single window and the seek loop; TF:241-381): one more decoder pass over the
         finished sequences and three kernels (alignment.extract_token_timestamps) -- the result is a dict {"sequences",
         "token_timestamps"[, "segments"]} as in the reference (TF:941-968); `attention_mask` gives the valid frames per row;
@@ -816,6 +823,19 @@ class WhisperForConditionalGeneration(nn.Module):
                                           "single-window decoding with the KV cache (not with beams, an assistant or use_cache=False)")
         if gc.decoder_start_token_id is None:
             gc.decoder_start_token_id = d.decoder_start_token_id
+        # ---- per-step scores (TF:generation/utils.py `_sample`: `scores` / `raw_logits`); without return_dict_in_generate the
+        # reference drops both flags, and so does this path
+        as_dict = bool(return_dict_in_generate or getattr(gc, "return_dict_in_generate", False))
+        want_scores = as_dict and bool(getattr(gc, "output_scores", False))
+        want_logits = as_dict and bool(getattr(gc, "output_logits", False))
+        if want_scores or want_logits:
+            what = " / ".join(n for n, w in (("output_scores", want_scores), ("output_logits", want_logits)) if w)
+            for on, combo in ((num_beams > 1, "beam search (num_beams > 1)"),
+                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
+                              (soft is not None, "sampling / repetition_penalty / no_repeat_ngram_size")):
+                if on:
+                    raise NotImplementedError(f"{what} combined with {combo} is not implemented on the MI355X path (per-step "
+                                              "scores come from single-window greedy search)")
         # ---- token-level timestamps (TF:1685-1700 `_set_num_frames`): what the alignment pass needs, or a loud refusal
         token_ts = None
         if return_token_timestamps:
@@ -871,6 +891,10 @@ class WhisperForConditionalGeneration(nn.Module):
                 if soft is not None:
                     raise NotImplementedError("sampling / repetition_penalty / no_repeat_ngram_size are implemented for "
                                               "single-window decoding, not inside the timestamp seek loop, on the MI355X path")
+                if want_scores or want_logits:
+                    raise NotImplementedError("output_scores / output_logits inside the timestamp seek loop (return_timestamps=True "
+                                              "without force_unique_generate_call, or more than 30 s of input) are not implemented "
+                                              "on the MI355X path")
                 return self._generate_seek_loop(input_features, attention_mask, gc, language, task, is_multilingual,
                                                 prompt_ids, kwargs, use_graphs, return_dict_in_generate, num_beams,
                                                 fallback_args, return_segments, token_ts)
@@ -991,22 +1015,41 @@ class WhisperForConditionalGeneration(nn.Module):
                 raise ValueError("return_timestamps=True runs on the KV-cache decoder (use_cache=True)")
             seqs = self._greedy_no_cache(enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress)
         seqs = self._trim_finished(seqs, P, eos, pad)
+        step_scores = step_logits = None
+        if want_scores or want_logits:
+            # one teacher-forced pass over the finished sequences + csrc/score.hip (scoring.py says why a second pass)
+            from .scoring import score_sequences
+            ts_rules = None
+            if gc.return_timestamps:
+                ts_rules = dict(no_timestamps_token_id=int(gc.no_timestamps_token_id),
+                                max_initial_timestamp_index=getattr(gc, "max_initial_timestamp_index", None))
+            step_scores, step_logits = score_sequences(
+                self, seqs, enc, P, dict(suppress_tokens=suppress, begin_suppress_tokens=begin_suppress, min_new_tokens=min_new,
+                                         eos_token_id=eos, timestamp_rules=ts_rules), want_scores, want_logits)
         if token_ts is not None:
             # TF:1146-1157: one alignment pass over the finished sequences; which shape comes back: TF:913-968
             from .alignment import extract_token_timestamps
             ts = extract_token_timestamps(self, seqs, enc, token_ts["alignment_heads"], token_ts["num_frames"], P,
                                           token_ts["time_precision"])
-            if return_dict_in_generate or getattr(gc, "return_dict_in_generate", False):
-                return G.GenerateOutput(seqs, token_timestamps=ts)
+            if as_dict:
+                return G.GenerateOutput(seqs, scores=step_scores, token_timestamps=ts, logits=step_logits)
             if force_unique_generate_call:
                 return {"sequences": seqs, "token_timestamps": ts}
             plain, plain_ts = G.strip_and_pad(seqs, P, eos, pad, token_timestamps=ts)
             return {"sequences": plain, "token_timestamps": plain_ts}
-        if return_dict_in_generate or getattr(gc, "return_dict_in_generate", False):
-            return G.GenerateOutput(seqs)
+        if as_dict:
+            return G.GenerateOutput(seqs, scores=step_scores, logits=step_logits)
         if force_unique_generate_call:
             return seqs
         return G.strip_and_pad(seqs, P, eos, pad)
+
+    def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
+        """`GenerationMixin.compute_transition_scores`: f32 [batch, steps], the score of every generated token of `sequences` in
+        `scores` (what `generate(output_scores=True, return_dict_in_generate=True)` returned as `.scores` or `.logits`), its
+        log-probability with `normalize_logits=True`.  For this package's tuples these are the values csrc/score.hip computed
+        next to the scores; foreign tensors go through the reference's gather.  `beam_indices` raises (no scores under beams)."""
+        from .scoring import compute_transition_scores
+        return compute_transition_scores(sequences, scores, beam_indices, normalize_logits)
 
     def seek_decode(self, input_features, max_frames, init_tokens, lengths, eos, pad, no_timestamps_token_id,
                     max_initial_timestamp_index=None, suppress_tokens=None, begin_suppress_tokens=None,

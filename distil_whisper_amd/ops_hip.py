@@ -105,6 +105,9 @@ _SIGS = {
                           C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "dw_dtw": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                 C.c_void_p], C.c_int),
+    "dw_score_tokens": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                         C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                         C.c_void_p, C.c_void_p], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
@@ -665,6 +668,32 @@ class HipOps:
                                   self._stream()), "dtw")
         return first_frame
 
+    # ---- scores of finished sequences (csrc/score.hip; TF:generation/utils.py `_sample` scores / raw_logits) ----------------
+    def score_tokens(self, logits, V, tokens, begin_index, L, *, batch_rows=None, suppress=None, begin_suppress=None, min_new=0,
+                     ts_begin=-1, max_initial=-1, eos=-1, want_scores=True, want_chosen=True):
+        """The reference's logits processors over the logits of a teacher-forced pass: logits bf16 / f32 [>= (B - 1) * batch_rows
+        + L, ld], row b * batch_rows + j predicts tokens[b, begin_index + j] (batch_rows defaults to L); tokens int64 [B, >=
+        begin_index + L]; masks uint8 [V].  -> (scores f32 [L, B, V] -- a view of a buffer whose rows are padded to a multiple of
+        four columns --: the logit where the column is allowed, -inf where a rule masks it; chosen f32 [B, L]: the processed
+        score of each token of `tokens`; logprob f32 [B, L]: its log_softmax over the processed row).  want_scores / want_chosen
+        False: that result is None (chosen and logprob come together).  With no rule argument given nothing is masked."""
+        B = tokens.shape[0]
+        rows = int(L) if batch_rows is None else int(batch_rows)
+        assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[1] >= begin_index + L
+        assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[1] >= V and rows >= L
+        assert logits.shape[0] >= (B - 1) * rows + L
+        for m in (suppress, begin_suppress):
+            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
+        ldo = _rup4(V)
+        scores = self.empty((L, B, ldo), torch.float32) if want_scores else None
+        chosen = self.empty((B, L), torch.float32) if want_chosen else None
+        logprob = self.empty((B, L), torch.float32) if want_chosen else None
+        self._chk(self.lib.dw_score_tokens(_p(logits), _dt(logits), B, int(L), int(V), logits.stride(0), rows, _p(tokens),
+                                           tokens.stride(0), int(begin_index), _p(suppress), _p(begin_suppress), int(min_new),
+                                           int(ts_begin), int(max_initial), int(eos), _p(scores), ldo, _p(chosen), _p(logprob),
+                                           self._stream()), "score_tokens")
+        return (None if scores is None else scores[:, :, :V]), chosen, logprob
+
     def adamw(self, p, g, m, v, shadow, sumsq, max_norm, grad_mul, lr, beta1, beta2, eps, weight_decay, step):
         assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
         self._chk(self.lib.dw_adamw(_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), _p(sumsq), float(max_norm),
@@ -703,5 +732,5 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("sumsq", "sumsq"), ("embed_fwd", "embed"), ("embed_bwd", "embed"), ("im2col_mel", "conv_aux"),
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),
                     ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("cross_attn_probs", "align"),
-                    ("align_prepare", "align"), ("dtw", "align")):
+                    ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score")):
     setattr(HipOps, _name, _timed(_key)(getattr(HipOps, _name)))

@@ -332,6 +332,25 @@ int dw_align_prepare(const float* probs, int B, int n_heads, int L, int64_t ldp,
 int dw_dtw(const float* cost, int B, int L, int64_t ldc, const int32_t* n_tok, const int32_t* n_frames, int max_frames,
            uint32_t* trace, int64_t trace_ld, int32_t* first_frame, void* stream);
 
+/* ---- scores of finished sequences (TF:generation/utils.py `_sample`: the per-step `scores` -- logits after the processors -- and
+ * `raw_logits` that `generate(output_scores=True / output_logits=True, return_dict_in_generate=True)` returns, and what
+ * `compute_transition_scores` and `_retrieve_avg_logprobs`, TF:models/whisper/generation_whisper.py:1958-1975, read from them).
+ * The logits come from ONE teacher-forced decoder pass over the finished sequences; this entry applies the processors of
+ * dw_greedy_select to every (step, row) at once.  logits: DW_BF16 or DW_F32 (dtype), row (b, j) at element offset
+ * (b * batch_rows + j) * ld, V valid columns (ld >= V, a multiple of 4; base 8- / 16-byte aligned) -- the row that predicts
+ * tokens[b][begin_index + j], j < L.  tokens int64 [B][tok_ld], tok_ld >= begin_index + L; begin_index = length of the decoder
+ * prompt.  suppress / begin_suppress: uint8 [V] masks or NULL (begin_suppress applies at j == 0 only); eos is masked while
+ * j < min_new; ts_begin / max_initial / eos as in dw_greedy_select (ts_begin < 0: no timestamp rules).  Outputs, each may be NULL
+ * (not all three): scores f32 [L][B][ld_scores] (ld_scores >= V, a multiple of 4, 16-byte aligned base): the logit itself where
+ * the column is allowed, -inf where a rule masks it and in the pad columns; chosen f32 [B][L]: the processed score of
+ * tokens[b][begin_index + j]; logprob f32 [B][L]: log_softmax of the processed row at that token (-inf when it is masked).
+ * With suppress = begin_suppress = NULL, min_new = 0 and ts_begin < 0 nothing is masked: a widening copy of the raw logits.
+ * One launch on `stream`; nothing is allocated, nothing synchronises.  B <= 65535. */
+int dw_score_tokens(const void* logits, int dtype, int B, int L, int V, int64_t ld, int64_t batch_rows, const int64_t* tokens,
+                    int64_t tok_ld, int begin_index, const uint8_t* suppress, const uint8_t* begin_suppress, int min_new,
+                    int ts_begin, int max_initial, int eos, float* scores, int64_t ld_scores, float* chosen, float* logprob,
+                    void* stream);
+
 /* ---- self tests (diagnostics for bring-up; not on the hot path) --------------------------------------------------
  * Runs ds_read_b64_tr_b16 on a known LDS image: out int32 [64][4] = element ids received by each lane. */
 int dw_selftest_tr16(int32_t* out, void* stream);
