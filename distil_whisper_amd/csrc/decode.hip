@@ -45,13 +45,22 @@ __device__ __forceinline__ Best block_best(Best x, Best* red) {
     return t;
 }
 
+// HIST (dw_greedy_select_history): the two history-dependent default processors of GenerationMixin, which the reference runs in
+// front of Whisper's own (TF `_get_logits_processor`): RepetitionPenaltyLogitsProcessor -- a column whose id occurs in
+// tokens[b, 0:n] (decoder prompt included) takes v < 0 ? v * p : v / p, once however often it occurs -- and
+// NoRepeatNGramLogitsProcessor -- a column that would complete an n-gram the row already holds is excluded.  Both are
+// predicates on (column, row history) like the rest: the workgroup turns the <= 448 history tokens into two bitmaps in LDS
+// (one bit per column: `seen`, `banned`); a four-column chunk whose bits are all clear keeps the short path of `judge`.
+#define SEL_HIST_V 65536                            // bitmap capacity in columns (2 x 8 KB of LDS)
+template <bool HIST>
 __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     const bf16* logits, int V, long ld, const uint8_t* suppress, const uint8_t* begin_suppress, int first, int no_eos,
     int forced, int tb, int max_initial, int64_t* tokens, long tok_ld, int n, int begin_index, int eos, int fill,
-    uint8_t* done, int64_t* cur) {
+    uint8_t* done, int64_t* cur, float rep_pen, int ngram) {
     __shared__ Best red[SEL_NT / 64];
     __shared__ float redf[SEL_NT / 64];
     __shared__ int redi[SEL_NT / 64];
+    __shared__ unsigned seen[HIST ? SEL_HIST_V / 32 : 1], banned[HIST ? SEL_HIST_V / 32 : 1];
     const int b = blockIdx.x, tid = threadIdx.x;
     int64_t* row_tok = tokens + (long)b * tok_ld;
     if (forced) {                                  // position n still belongs to the forced prefix (teacher forcing)
@@ -59,6 +68,24 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
         return;
     }
     const bf16* row = logits + (long)b * ld;
+    if constexpr (HIST) {
+        for (int w = tid; w < SEL_HIST_V / 32; w += SEL_NT) { seen[w] = 0u; banned[w] = 0u; }
+        __syncthreads();
+        const int g = ngram;
+        for (int i = tid; i < n; i += SEL_NT) {
+            const long t = row_tok[i];
+            if (t < 0 || t >= V) continue;                                  // (no column: nothing to mark)
+            const unsigned bit = 1u << ((int)t & 31);
+            if (rep_pen != 1.0f) atomicOr(&seen[(int)t >> 5], bit);
+            if (g > 0 && i >= g - 1) {                                      // tokens[i] followed the window [i - g + 1, i)
+                bool hit = true;                                            // (n >= g here; g = 1: an empty window)
+                for (int k = 1; k < g && hit; ++k) hit = row_tok[i - k] == row_tok[n - k];
+                if (hit) atomicOr(&banned[(int)t >> 5], bit);
+            }
+        }
+        __syncthreads();
+    }
+    auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
     const bool ts_mode = tb >= 0;
     const int tsb = ts_mode ? tb : V + 1;          // first timestamp id (beyond the vocabulary when the rules are off)
     // ---- row state of the timestamp rules (WhisperTimeStampLogitsProcessor) ----
@@ -102,6 +129,7 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     auto allowed = [&](int c) -> bool {               // (used by the probability-mass pass below)
         if (suppress && suppress[c]) return false;
         if (first && begin_suppress && begin_suppress[c]) return false;
+        if constexpr (HIST) { if ((banned[c >> 5] >> (c & 31)) & 1u) return false; }
         return ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots;
     };
     // ---- pass 1: best allowed text token and best allowed timestamp token ----
@@ -128,8 +156,14 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     auto judge = [&](int c0, const bf16x4& x, unsigned mask, bool live) {
         const int c3 = c0 + 3;
         const bool in_text = c0 >= tlo && c3 < thi, in_ts = c0 >= slo && c3 < shi;
-        const bool clean = live && mask == 0 && c3 < V && (in_text || in_ts) && !(ban_eos >= c0 && ban_eos <= c3) &&
-                           !(ban_nots >= c0 && ban_nots <= c3);
+        bool clean = live && mask == 0 && c3 < V && (in_text || in_ts) && !(ban_eos >= c0 && ban_eos <= c3) &&
+                     !(ban_nots >= c0 && ban_nots <= c3);
+        unsigned sbits = 0, bbits = 0;                 // bit e: column c0 + e is in the history / banned (c0 is a multiple of 4)
+        if constexpr (HIST) {
+            sbits = (seen[c0 >> 5] >> (c0 & 31)) & 0xfu;
+            bbits = (banned[c0 >> 5] >> (c0 & 31)) & 0xfu;
+            clean = clean && (sbits | bbits) == 0;
+        }
         if (clean) {
             float bv = in_text ? bt.v : bs.v;
             int bi = in_text ? bt.i : bs.i;
@@ -145,9 +179,12 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
         for (int e = 0; e < 4; ++e) {
             const int c = c0 + e;
             const bool ok = live && c < V && !((mask >> (8 * e)) & 0xffu) &&
-                            ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots;
+                            ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots &&
+                            !((bbits >> e) & 1u);
             if (ok) {
-                const Best cand = {bf2f(x[e]), c};
+                float v = bf2f(x[e]);
+                if constexpr (HIST) { if ((sbits >> e) & 1u) v = penal(v); }
+                const Best cand = {v, c};
                 if (c < tsb) bt = better(bt, cand); else bs = better(bs, cand);
             }
         }
@@ -180,7 +217,11 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
         // sampled mass rule: if logsumexp over the allowed timestamps exceeds the best text logit, a timestamp is taken
         float sum = 0.f;
         for (int c = tsb + tid; c < V; c += SEL_NT)
-            if (allowed(c)) sum += __expf(bf2f(row[c]) - bs.v);
+            if (allowed(c)) {
+                float v = bf2f(row[c]);
+                if constexpr (HIST) { if ((seen[c >> 5] >> (c & 31)) & 1u) v = penal(v); }
+                sum += __expf(v - bs.v);
+            }
         sum = wave_sum(sum);
         __syncthreads();
         if ((tid & 63) == 0) redf[tid >> 6] = sum;
@@ -211,9 +252,29 @@ extern "C" int dw_greedy_select(const void* logits, int B, int V, int64_t ld, co
         if (eos >= 0 && !done) return DW_EINVAL;
         if (ts_begin >= 0 && (eos < 0 || begin_index < 1 || begin_index > n)) return DW_EINVAL;
     }
-    hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V,
+    hipLaunchKernelGGL(greedy_select_kernel<false>, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V,
                        (long)ld, suppress, begin_suppress, first, no_eos, forced, ts_begin, max_initial, tokens,
-                       (long)tok_ld, n, begin_index, eos, fill, done, cur);
+                       (long)tok_ld, n, begin_index, eos, fill, done, cur, 1.0f, 0);
+    DW_CHECK_LAUNCH();
+    return DW_OK;
+}
+
+extern "C" int dw_greedy_select_history(const void* logits, int B, int V, int64_t ld, const uint8_t* suppress,
+                                        const uint8_t* begin_suppress, int first, int no_eos, int forced, int ts_begin,
+                                        int max_initial, int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos,
+                                        int fill, uint8_t* done, int64_t* cur, float repetition_penalty, int no_repeat_ngram,
+                                        void* stream) {
+    DW_CLEAR_ERR();
+    if (!tokens || !cur || B <= 0 || n < 1 || n >= tok_ld) return DW_EINVAL;
+    if (!(repetition_penalty > 0.f) || !(repetition_penalty <= 3.402823466e38f) || no_repeat_ngram < 0) return DW_EINVAL;
+    if (!forced) {
+        if (!logits || V <= 0 || V > SEL_HIST_V || ld < V || (ld & 3) || ((uintptr_t)logits & 7)) return DW_EINVAL;
+        if (eos >= 0 && !done) return DW_EINVAL;
+        if (ts_begin >= 0 && (eos < 0 || begin_index < 1 || begin_index > n)) return DW_EINVAL;
+    }
+    hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V,
+                       (long)ld, suppress, begin_suppress, first, no_eos, forced, ts_begin, max_initial, tokens,
+                       (long)tok_ld, n, begin_index, eos, fill, done, cur, repetition_penalty, no_repeat_ngram);
     DW_CHECK_LAUNCH();
     return DW_OK;
 }

@@ -133,11 +133,21 @@ class GreedyDecoder:
         # soft = dict(do_sample=, temperature=, top_k=, top_p=, repetition_penalty=, no_repeat_ngram_size=, generator=):
         # history-dependent processors and sampling of `GenerationMixin` (TF `_get_logits_processor` order: repetition
         # penalty, no-repeat n-gram, min-new-tokens, Whisper's suppress / begin-suppress / timestamp rules, then the
-        # temperature / top-k / top-p warpers and the multinomial draw).  The selection then runs as torch ops on the
-        # step's logits instead of dw_greedy_select, eagerly (no HIP-graph replay: the history grows every step).
+        # temperature / top-k / top-p warpers and the multinomial draw).
+        # Without sampling the two history rules run inside the selection kernel (dw_greedy_select_history: the history is the
+        # `tokens` buffer the kernel reads anyway, so the step stays one launch and is captured into the per-position graphs
+        # like the plain one).  With sampling -- whose parity with the reference rests on torch.multinomial -- or on ops
+        # without that entry (the torch restatement oracle.ref_ops) the selection runs as torch ops on the step's logits,
+        # eagerly, without HIP-graph replay.
         self.soft = soft
+        self.history = None
         if soft is not None:
-            self.use_graphs = False
+            rp, ng = soft.get("repetition_penalty"), int(soft.get("no_repeat_ngram_size") or 0)
+            rp = 1.0 if rp is None else float(rp)
+            if not soft.get("do_sample") and (rp != 1.0 or ng) and hasattr(engine.ops, "greedy_select_history"):
+                self.history = dict(repetition_penalty=rp, no_repeat_ngram=ng)
+            else:
+                self.use_graphs = False
         self.cache = None
         self.graphs = {}
         self.pool = None
@@ -149,19 +159,22 @@ class GreedyDecoder:
         self.cache["t"] = t
         logits = eng.decode_step(self.cur, self.cache)
         r = self.timestamp_rules
-        if self.soft is not None and mode != 0:
+        if self.soft is not None and self.history is None and mode != 0:
             self._select_soft(logits, t + 1, mode, no_eos)
             return
         # logits processors of the reference (min-new-tokens, begin-suppress, suppress, timestamp rules), argmax and the
         # EOS bookkeeping in one launch (csrc/decode.hip); the next token lands in tokens[:, t+1] and in cur
-        eng.ops.greedy_select(
+        select, hist = eng.ops.greedy_select, {}
+        if self.history is not None:
+            select, hist = eng.ops.greedy_select_history, self.history
+        select(
             logits, d.vocab, self.tokens, t + 1, self.cur, suppress=self.suppress, begin_suppress=self.begin_suppress,
             first=(mode == 1), no_eos=no_eos, forced=(mode == 0),
             ts_begin=-1 if r is None else r["no_timestamps_token_id"] + 1,
             max_initial=-1 if (r is None or r.get("max_initial_timestamp_index") is None)
             else r["max_initial_timestamp_index"],
             begin_index=1 if r is None else r["begin_index"], eos=-1 if self.eos is None else self.eos,
-            fill=self.fill, done=self.done)
+            fill=self.fill, done=self.done, **hist)
 
     def _select_soft(self, logits, n, mode, no_eos):
         """Token n of every row from `logits` with the history-dependent processors / sampling of `self.soft`."""

@@ -200,6 +200,20 @@ def two_stage_pipeline(owner, ops, dev, batches, encode_fn, decode_fn, overlap, 
         main.wait_stream(s_dec)
 
 
+def history_soft(repetition_penalty, no_repeat_ngram_size):
+    """The `soft` argument of decoding.GreedyDecoder for greedy decoding under `repetition_penalty` / `no_repeat_ngram_size`
+    (None when both are off)."""
+    rp = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
+    ng = int(no_repeat_ngram_size or 0)
+    if rp is not None and not rp > 0.0:
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
+    if ng < 0:
+        raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer or 0, but is {no_repeat_ngram_size}")
+    if rp is None and not ng:
+        return None
+    return dict(do_sample=False, repetition_penalty=rp, no_repeat_ngram_size=ng)
+
+
 class LongFormTranscriber:
     """audio (list of 1-D float tensors/arrays at 16 kHz, any length) -> list of stitched text-token id lists."""
 
@@ -207,8 +221,10 @@ class LongFormTranscriber:
                  max_new_tokens=128, prompt_ids=None, eos_token_id=None, first_special_id=None, suppress_tokens=None,
                  begin_suppress_tokens=None, use_graphs=None, rank=0, world=1, return_timestamps=False,
                  no_timestamps_token_id=None, max_initial_timestamp_index=50, special_ids=None, overlap=False,
-                 decode_cus=64):
-        """return_timestamps=True: the windows are decoded under the timestamp rules (`prompt_ids` must then not end in
+                 decode_cus=64, repetition_penalty=None, no_repeat_ngram_size=0):
+        """repetition_penalty / no_repeat_ngram_size: GenerationMixin's two rules against repetition loops, applied per window
+        by the selection kernel inside the graph-captured token step (decoding.GreedyDecoder `soft`).
+        return_timestamps=True: the windows are decoded under the timestamp rules (`prompt_ids` must then not end in
         <|notimestamps|>; `no_timestamps_token_id` is required) and stitched by their timestamp tokens; the call returns
         per utterance a list of {"timestamp": (start, end), "tokens": [...]} (`stitch_timestamped`)."""
         self.model, self.fe = model, feature_extractor
@@ -257,7 +273,8 @@ class LongFormTranscriber:
                          max_initial_timestamp_index=max_initial_timestamp_index)
         self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
                                      suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                     use_graphs=use_graphs, timestamp_rules=rules)
+                                     use_graphs=use_graphs, timestamp_rules=rules,
+                                     soft=history_soft(repetition_penalty, no_repeat_ngram_size))
         self._wave = torch.zeros((self.B, feature_extractor.n_samples), dtype=torch.float32, device=dev)
         # overlap=True (GPU only): the encoder of batch i+1 runs on one HIP stream while the token loop of batch i runs on
         # another.  A batch of 16 windows is ~41 ms of encoder (MFMA-bound, persistent GEMM grids on every CU) followed by ~32 ms

@@ -756,11 +756,14 @@ class WhisperForConditionalGeneration(nn.Module):
         `force_unique_generate_call`) and inputs longer than 30 s run the reference's timestamp seek loop
         (`seek_decode`, TF:784-903) with `condition_on_prev_tokens`, the fallback thresholds (`temperature` tuple,
         `compression_ratio_threshold`, `logprob_threshold`) and the `no_speech_threshold` skip.
-        Single-window greedy decoding also takes GenerationMixin's `repetition_penalty`, `no_repeat_ngram_size` and plain
-        sampling (a positive `temperature`, as in the reference's generate_with_fallback, with `top_k` / `top_p`):
-        decoding.GreedyDecoder `soft` -- token for token the reference's on the same device and seed.
+        Greedy decoding also takes GenerationMixin's `repetition_penalty` and `no_repeat_ngram_size`, in one window and in the
+        seek loop: the selection kernel applies them (dw_greedy_select_history), so `use_graphs=True` holds with them.
+        Single-window decoding takes plain sampling as well (a positive `temperature`, as in the reference's
+        generate_with_fallback, with `top_k` / `top_p`): decoding.GreedyDecoder `soft`, eager torch ops -- token for token the
+        reference's on the same device and seed.
         Arguments this path does not implement RAISE (nothing is silently ignored): group beam search, those three options
-        combined with beams / an assistant / the seek loop, the fallback heuristics outside the seek loop, custom logits
+        combined with beams / an assistant / `use_cache=False`, plain sampling inside the seek loop, the two history options with
+        `condition_on_prev_tokens=True` over several utterances, the fallback heuristics outside the seek loop, custom logits
         processors, `return_token_timestamps` combined with beams / an assistant / sampling / the fallback heuristics.
         `output_scores=True` / `output_logits=True` with `return_dict_in_generate=True` (single-window greedy search, with or
         without the KV cache, HIP graphs, prompt_ids / decoder_input_ids / encoder_outputs, the timestamp rules under
@@ -888,16 +891,18 @@ class WhisperForConditionalGeneration(nn.Module):
             if frames > 2 * d.max_src or (rt and not force_unique_generate_call):
                 # the reference's seek loop (TF:784-903): with timestamps every window is decoded until its audio is
                 # consumed, also when the input is a single 30 s window (run_pseudo_labelling.py:861-996 calls it so)
-                if soft is not None:
-                    raise NotImplementedError("sampling / repetition_penalty / no_repeat_ngram_size are implemented for "
-                                              "single-window decoding, not inside the timestamp seek loop, on the MI355X path")
+                if sample_temp is not None:
+                    raise NotImplementedError("sampling (a positive temperature as a plain switch) is implemented for "
+                                              "single-window decoding, not inside the timestamp seek loop, on the MI355X path "
+                                              "(a temperature tuple runs the seek loop's sampled fallback passes)")
                 if want_scores or want_logits:
                     raise NotImplementedError("output_scores / output_logits inside the timestamp seek loop (return_timestamps=True "
                                               "without force_unique_generate_call, or more than 30 s of input) are not implemented "
                                               "on the MI355X path")
                 return self._generate_seek_loop(input_features, attention_mask, gc, language, task, is_multilingual,
                                                 prompt_ids, kwargs, use_graphs, return_dict_in_generate, num_beams,
-                                                fallback_args, return_segments, token_ts)
+                                                fallback_args, return_segments, token_ts,
+                                                history=dict(repetition_penalty=rp, no_repeat_ngram_size=nrn))
             if return_segments:
                 raise NotImplementedError("return_segments comes with the timestamp seek loop (return_timestamps=True) "
                                           "on the MI355X path")
@@ -1056,7 +1061,7 @@ class WhisperForConditionalGeneration(nn.Module):
                     detect_language=None, temperatures=(0.0,), compression_ratio_threshold=None, logprob_threshold=None,
                     no_speech_threshold=None, condition_on_prev_tokens=False, prev_sot_token_id=None, prompt_ids=None,
                     prompt_all_segments=False, num_beams=1, length_penalty=1.0, early_stopping=False, assistant=None,
-                    num_assistant_tokens=5, token_timestamps=None):
+                    num_assistant_tokens=5, token_timestamps=None, repetition_penalty=None, no_repeat_ngram_size=0):
         """The seek loop itself (TF:generation_whisper.py:784-903): input_features [B, n_mels, frames], max_frames[b] =
         valid mel frames of utterance b.  init_tokens: the decoder prompt rows (list of B lists) or a callable(detect)
         building them (detect() = language ids from the first window); lengths(P) -> (max_new_tokens, min_new_tokens)
@@ -1086,13 +1091,32 @@ class WhisperForConditionalGeneration(nn.Module):
             batch goes through alignment.extract_token_timestamps with `num_frames - seek` of its rows (TF:1146-1157); a segment
             then carries "token_timestamps" (its tokens' times plus the window's offset, TF:2034-2036, 2068-2070) and, as in the
             reference, "result" = {"token_timestamps": the window's row} with "idxs" = the segment's slice of it.
+          * repetition_penalty / no_repeat_ngram_size (the reference hands its generation config to GenerationMixin.generate for
+            every window, TF `generate_with_fallback`): the greedy pass of a window runs them inside the selection kernel
+            (decoding.GreedyDecoder `soft`), over the window's decoder prompt and tokens -- previous-text prompt included;
+            sampled fallback passes and the threshold scores see them through `processed`.  Not with beams or an assistant,
+            and not with condition_on_prev_tokens over several utterances (see the message below).
         -> per utterance the list of segments {"start", "end", "tokens"}."""
         import math
         import zlib
         from . import generation as G
-        from .decoding import GreedyDecoder, apply_timestamp_rules
+        from .decoding import GreedyDecoder, apply_no_repeat_ngram, apply_repetition_penalty, apply_timestamp_rules
         eng, d = self.engine, self.dims
         B = input_features.shape[0]
+        rep_pen = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
+        ngram = int(no_repeat_ngram_size or 0)
+        hist_soft = None
+        if rep_pen is not None or ngram:
+            if int(num_beams) > 1 or assistant is not None:
+                raise NotImplementedError("repetition_penalty / no_repeat_ngram_size inside the timestamp seek loop are "
+                                          "implemented for greedy passes (not with beams or an assistant) on the MI355X path")
+            if condition_on_prev_tokens and B > 1:
+                raise NotImplementedError(
+                    "repetition_penalty / no_repeat_ngram_size with condition_on_prev_tokens=True and more than one utterance "
+                    "are not implemented on the MI355X path: the reference left-pads that batch with pad_token_id and its "
+                    "processors then count the pads as history, while this package decodes rows in groups of equal prompt "
+                    "length (no pads).  Pass one utterance per call")
+            hist_soft = dict(do_sample=False, repetition_penalty=rep_pen, no_repeat_ngram_size=ngram)
         dev = input_features.device
         W, V = 2 * d.max_src, d.vocab
         feats = input_features.to(torch.float32)
@@ -1137,6 +1161,10 @@ class WhisperForConditionalGeneration(nn.Module):
         def processed(raw, hist, n, P, min_new):
             """The reference's processed scores of one step: raw f32 [r, V], hist int64 [r, >= n] (n tokens so far)."""
             sc = raw.clone()
+            if rep_pen is not None:        # GenerationMixin's own processors come first (TF `_get_logits_processor`)
+                sc = apply_repetition_penalty(sc, hist[:, :n], rep_pen)
+            if ngram:
+                sc = apply_no_repeat_ngram(sc, hist[:, :n], ngram)
             if n - P < min_new:
                 sc[:, eos] = float("-inf")
             if n == P:
@@ -1267,7 +1295,7 @@ class WhisperForConditionalGeneration(nn.Module):
                                                  max_initial_timestamp_index=max_initial_timestamp_index))[:, P:].tolist()
                     else:
                         key = (len(pending), P, max_new, eos, pad, nts, max_initial_timestamp_index,
-                               tuple(suppress_tokens or ()), tuple(begin_suppress_tokens or ()))
+                               tuple(suppress_tokens or ()), tuple(begin_suppress_tokens or ()), rep_pen, ngram)
                         dec = decoders.get(key)
                         if dec is None:
                             if len(decoders) >= 4:     # (a decoder owns its K/V caches: keep a handful alive)
@@ -1277,7 +1305,8 @@ class WhisperForConditionalGeneration(nn.Module):
                                 begin_suppress_tokens=begin_suppress_tokens, use_graphs=False, pad_token_id=pad,
                                 check_every=4,      # eager passes: stop within 3 steps of the last row's EOS
                                 timestamp_rules=dict(begin_index=P, no_timestamps_token_id=nts,
-                                                     max_initial_timestamp_index=max_initial_timestamp_index))
+                                                     max_initial_timestamp_index=max_initial_timestamp_index),
+                                soft=hist_soft)
                         full = dec.run(enc, ids, max_new, min_new)
                         if token_timestamps is not None:
                             from .alignment import extract_token_timestamps
@@ -1339,7 +1368,7 @@ class WhisperForConditionalGeneration(nn.Module):
 
     def _generate_seek_loop(self, input_features, attention_mask, gc, language, task, is_multilingual, prompt_ids, kwargs,
                             use_graphs, return_dict_in_generate, num_beams, fallback_args=None, return_segments=False,
-                            token_ts=None):
+                            token_ts=None, history=None):
         """Timestamp-driven multi-pass transcription: `WhisperGenerationMixin.generate` steps 5-7 (TF:745-968) with
         temperature 0 and no fallback thresholds -- every utterance keeps a `seek` position in mel frames; each pass
         decodes the next <= 30 s window of every unfinished utterance with the timestamp rules, `retrieve_segment`
@@ -1419,7 +1448,7 @@ class WhisperForConditionalGeneration(nn.Module):
                                         getattr(am, "generation_config", None), "num_assistant_tokens", None) or 5),
                                     length_penalty=1.0 if getattr(gc, "length_penalty", None) is None else gc.length_penalty,
                                     early_stopping=getattr(gc, "early_stopping", False) or False,
-                                    token_timestamps=token_ts, **(fallback_args or {}))
+                                    token_timestamps=token_ts, **(history or {}), **(fallback_args or {}))
         rows_out = [[tok for sg in segments[b] for tok in sg["tokens"]] for b in range(B)]
         width = max((len(r) for r in rows_out), default=0)
         seqs = torch.full((B, width), pad, dtype=torch.long, device=dev)

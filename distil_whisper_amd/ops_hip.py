@@ -99,6 +99,9 @@ _SIGS = {
     "dw_greedy_select": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                          [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                           C.c_void_p], C.c_int),
+    "dw_greedy_select_history": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                                 [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_float, C.c_int, C.c_void_p], C.c_int),
     "dw_cross_attn_probs": ([C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int64,
                                                                                                     C.c_float, C.c_void_p], C.c_int),
     "dw_align_prepare": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -623,6 +626,24 @@ class HipOps:
                                             int(begin_index), int(eos), int(fill), _p(done), _p(cur), self._stream()),
                   "greedy_select")
 
+    def greedy_select_history(self, logits, V, tokens, n, cur, *, suppress=None, begin_suppress=None, first=False, no_eos=False,
+                              forced=False, ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, fill=-1, done=None,
+                              repetition_penalty=1.0, no_repeat_ngram=0):
+        """`greedy_select` with GenerationMixin's repetition penalty and no-repeat-n-gram rule in front of the other rules, in
+        the same single launch: the history of row b is tokens[b, :n] (decoder prompt included)."""
+        B = tokens.shape[0]
+        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous()
+        if not forced:
+            assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= B
+        for m in (suppress, begin_suppress):
+            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
+        assert done is None or (done.dtype == torch.bool and done.is_contiguous())
+        self._chk(self.lib.dw_greedy_select_history(
+            _p(logits), B, int(V), logits.stride(0) if logits is not None else 0, _p(suppress), _p(begin_suppress),
+            int(first), int(no_eos), int(forced), int(ts_begin), int(max_initial), _p(tokens), tokens.stride(0), int(n),
+            int(begin_index), int(eos), int(fill), _p(done), _p(cur), float(repetition_penalty), int(no_repeat_ngram),
+            self._stream()), "greedy_select_history")
+
     # ---- token-level timestamps (csrc/align.hip; TF:generation_whisper.py:241-381) ------------------------------------
     def cross_attn_probs(self, q, k, heads, probs, slot0, B, L, Lk, kv_batch_rows=None, scale=0.125):
         """probs[:, slot0:slot0 + len(heads), :, :Lk] = softmax(scale * q k^T) of the listed heads (int32, on the device).
@@ -731,6 +752,7 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("logmel", "logmel"), ("adamw", "adamw"), ("adamw_dev", "adamw"), ("cast_bf16", "cast"), ("colsum", "colsum"),
                     ("sumsq", "sumsq"), ("embed_fwd", "embed"), ("embed_bwd", "embed"), ("im2col_mel", "conv_aux"),
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),
-                    ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("cross_attn_probs", "align"),
+                    ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("greedy_select_history", "select"),
+                    ("cross_attn_probs", "align"),
                     ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score")):
     setattr(HipOps, _name, _timed(_key)(getattr(HipOps, _name)))

@@ -45,12 +45,22 @@ class PseudoLabeller:
 
     def __init__(self, model, feature_extractor, batch_size=16, max_new_tokens=255, prompt_ids=None, eos_token_id=None,
                  timestamp_rules=None, use_graphs=None, rank=0, world=1, suppress_tokens=None,
-                 begin_suppress_tokens=None, num_beams=1, overlap=False, decode_cus=64):
+                 begin_suppress_tokens=None, num_beams=1, overlap=False, decode_cus=64, repetition_penalty=None,
+                 no_repeat_ngram_size=0):
+        from .longform import history_soft
         self.model, self.fe = model, feature_extractor
         self.B, self.max_new = int(batch_size), int(max_new_tokens)
         self.rank, self.world = rank, world
         self.num_beams = int(num_beams)      # generation_num_beams of run_pseudo_labelling.py:835-843
         self._beam_kw = dict(suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens)
+        # GenerationMixin's two rules against repetition loops: inside the selection kernel of the graph-captured token step
+        # (decoding.GreedyDecoder `soft`) and of the seek loop's greedy passes; beam search does not take them
+        soft = history_soft(repetition_penalty, no_repeat_ngram_size)
+        if soft is not None and self.num_beams > 1:
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size with num_beams > 1 are not implemented on the "
+                                      "MI355X path (greedy decoding only)")
+        self._history_kw = {} if soft is None else dict(repetition_penalty=soft["repetition_penalty"],
+                                                        no_repeat_ngram_size=soft["no_repeat_ngram_size"])
         d = model.dims
         dev = model.ops.device
         self.dev = dev
@@ -62,7 +72,7 @@ class PseudoLabeller:
         self.eos = eos_token_id
         self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
                                      suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                     use_graphs=use_graphs, timestamp_rules=timestamp_rules)
+                                     use_graphs=use_graphs, timestamp_rules=timestamp_rules, soft=soft)
         self._wave = torch.zeros((self.B, feature_extractor.n_samples), dtype=torch.float32, device=dev)
         # overlap=True: the encoder of the next batch of packs beside the token loop of the current one (longform.two_stage_pipeline;
         # plain greedy decoding only -- the seek loop and beam search encode / decode in their own order)
@@ -114,7 +124,8 @@ class PseudoLabeller:
                 segs = model.seek_decode(feats[:nb], [feats.shape[-1]] * nb, [self.prompt.tolist()] * nb,
                                          lambda P: (self.max_new, 0), self.eos,
                                          self.eos, self._ts_rules["no_timestamps_token_id"],
-                                         self._ts_rules.get("max_initial_timestamp_index"), **self._beam_kw)
+                                         self._ts_rules.get("max_initial_timestamp_index"), **self._beam_kw,
+                                         **self._history_kw)
                 for r, pi in enumerate(batch):
                     out[pi] = [int(t) for sg in segs[r] for t in sg["tokens"]]
                 continue

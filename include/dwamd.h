@@ -259,6 +259,16 @@ int dw_greedy_select(const void* logits, int B, int V, int64_t ld, const uint8_t
                      const uint8_t* begin_suppress, int first, int no_eos, int forced, int ts_begin, int max_initial,
                      int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, int fill, uint8_t* done,
                      int64_t* cur, void* stream);
+/* The same step with the two history-dependent default processors of GenerationMixin in front of the rules above (TF
+ * `_get_logits_processor` order): RepetitionPenaltyLogitsProcessor -- the logit v of every id in tokens[b][0, n) (the decoder
+ * prompt included) becomes v < 0 ? v * repetition_penalty : v / repetition_penalty, once per id -- and
+ * NoRepeatNGramLogitsProcessor -- an id that would complete an n-gram of size no_repeat_ngram the row already holds is
+ * never selected (0 = off).  repetition_penalty must be finite and > 0 (1.0 = off), no_repeat_ngram >= 0, V <= 65536 (the
+ * history bitmaps of the workgroup); with 1.0 and 0 it selects what dw_greedy_select selects. */
+int dw_greedy_select_history(const void* logits, int B, int V, int64_t ld, const uint8_t* suppress,
+                             const uint8_t* begin_suppress, int first, int no_eos, int forced, int ts_begin, int max_initial,
+                             int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, int fill, uint8_t* done,
+                             int64_t* cur, float repetition_penalty, int no_repeat_ngram, void* stream);
 
 /* ---- a11: one decoder pass of cached greedy decoding as ONE call (the `decode_step` entry of SURVEY.md 8b).
  * Replaces `WhisperDecoder.forward` + `proj_out` on the cache branch (TF:modeling_whisper.py:690-795, 312-335, 1080)
