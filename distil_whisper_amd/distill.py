@@ -238,7 +238,7 @@ class DistillationTrainer:
                  lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, freeze_encoder=False,
                  share_encoder=False, freeze_embed_positions=False, process_group=None, mel_filters=None,
                  overlap_teacher=False, overlap_wgrad=False, pad_teacher_rows=False, bucket_bytes=256 << 20,
-                 always_reduce=False, comm_watchdog_s=0.0):
+                 always_reduce=False, comm_watchdog_s=0.0, dropout=None, activation_dropout=None, dropout_seed=0):
         self.ops = ops
         self.sdims, self.tdims = WhisperDims.from_any(student_dims), WhisperDims.from_any(teacher_dims)
         frozen = []
@@ -251,6 +251,16 @@ class DistillationTrainer:
         self.student = WhisperEngine(ops, self.student_store, torch.float32)
         self.teacher = WhisperEngine(ops, self.teacher_store, ops.lowp)
         self.teacher.pad_gemm_rows = bool(pad_teacher_rows)   # decoder GEMMs of the frozen teacher over M padded to 320 rows
+        # `dropout` / `activation_dropout` of the student's training forward (defaults: the student config's fields; the teacher,
+        # eval_step and a frozen encoder's forward-only pass never drop).  Every rank draws its own masks, as each rank's torch
+        # generator does in the reference: the effective seed is dropout_seed + rank.
+        import torch.distributed as dist
+        rank = dist.get_rank(process_group) if (dist.is_available() and dist.is_initialized()) else 0
+        self.dropout = float((getattr(student_dims, "dropout", 0.0) or 0.0) if dropout is None else dropout)
+        self.activation_dropout = float((getattr(student_dims, "activation_dropout", 0.0) or 0.0)
+                                        if activation_dropout is None else activation_dropout)
+        self.dropout_seed = int(dropout_seed) + rank
+        self.student.set_dropout(self.dropout, self.activation_dropout, seed=self.dropout_seed)
         self.temperature, self.kl_weight = temperature, kl_weight
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
@@ -331,8 +341,13 @@ class DistillationTrainer:
             # (no record_stream: the inputs are the caller's and stay alive over the call, the side stream is joined
             # below, and logits_t -- a block of the side stream's pool -- is next written by the teacher forward of the
             # following step, which starts with side.wait_stream(main), i.e. after the loss kernel that reads it)
-        enc_s, ectx = S.encode(input_features, save=not self.freeze_encoder)
-        logits_s, dctx = S.decode(decoder_input_ids, enc_s, save=True, live=live)
+        S.training = True
+        try:
+            S.dropout_tick()      # one per student forward, on the device: a captured step replays it (no launch with dropout off)
+            enc_s, ectx = S.encode(input_features, save=not self.freeze_encoder)
+            logits_s, dctx = S.decode(decoder_input_ids, enc_s, save=True, live=live)
+        finally:
+            S.training = False
         if side is not None:
             main.wait_stream(side)
         elif self.share_encoder:
@@ -587,11 +602,15 @@ class DistillationTrainer:
             for d in shape:
                 n *= d
             return buf[o:o + n].view(shape).detach().clone()
-        return {"model": st.state_dict(), "exp_avg": {n: view(st.M, n) for n in names},
-                "exp_avg_sq": {n: view(st.V, n) for n in names}, "step": self.step_count,
-                "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
-                          "max_grad_norm": self.max_grad_norm, "temperature": self.temperature,
-                          "kl_weight": self.kl_weight}}
+        state = {"model": st.state_dict(), "exp_avg": {n: view(st.M, n) for n in names},
+                 "exp_avg_sq": {n: view(st.V, n) for n in names}, "step": self.step_count,
+                 "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                           "max_grad_norm": self.max_grad_norm, "temperature": self.temperature,
+                           "kl_weight": self.kl_weight}}
+        if self.dropout or self.activation_dropout:       # a resumed run continues the mask sequence
+            state["dropout"] = {"dropout": self.dropout, "activation_dropout": self.activation_dropout,
+                                "seed": self.dropout_seed, "step": int(self.student.drop_state.item())}
+        return state
 
     def load_state_dict(self, state):
         st = self.student_store
@@ -609,4 +628,9 @@ class DistillationTrainer:
         self.segments = st.adam_segments(self.weight_decay)       # per-range weight decay follows the restored value
         self._adam = self.ops.adam_state(self.lr, self.betas[0], self.betas[1], int(state["step"]))
         self._lr_dev = self.lr
+        dr = state.get("dropout")
+        if dr is not None:
+            self.dropout, self.activation_dropout = float(dr["dropout"]), float(dr["activation_dropout"])
+            self.dropout_seed = int(dr["seed"])
+            self.student.set_dropout(self.dropout, self.activation_dropout, seed=self.dropout_seed, step=int(dr["step"]))
         self.drop_graph()         # (a captured step has the old hyper-parameters baked in: re-planned on next use)

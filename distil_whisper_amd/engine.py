@@ -305,6 +305,51 @@ class WhisperEngine:
         self.pad_gemm_rows_min = 2560       # smallest B*T worth padding
         self.pad_gemm_rows_slack = 1 / 32   # most extra rows accepted, as a fraction of B*T
         self.pad_lm_rows = True             # training passes: zero pad rows behind hf / logits for the LM-head backward
+        # Training-mode dropout (set_dropout): off unless the owner (DistillationTrainer / the drop-in module) switches it on
+        # AND marks the pass as a training pass (`training`); forward-only passes (save=False) never drop.
+        self.training = False
+        self.p_drop = self.p_act = 0.0
+        self.drop_seed, self.drop_state = 0, None
+        self.keep_masks = None      # tests: a dict that receives {site: mask buffer} of the last training forward
+
+    # ---- dropout -------------------------------------------------------------------------------------------------
+    # `dropout` (embeddings, the three residual branches) and `activation_dropout` (GELU output of fc1) of TF:modeling_whisper.py:
+    # 398-406, 479-502, 625, 763.  Masks come from a counter-based generator keyed by (seed, step, site, element) -- include/dwamd.h
+    # dw_dropout_fwd -- where `site` numbers the places a mask is drawn within one forward:
+    #     site = ((side * 64 + layer + 1) * 4 + kind)     side: 0 encoder, 1 decoder;  layer: -1 for the embedding, else the layer;
+    #     kind: 0 self-attention out_proj (and the embedding), 1 cross-attention out_proj, 2 fc2, 3 the fc1 activation
+    # and the element index runs over the rows in the order the engine processes them (packed order on the packed path).
+    @staticmethod
+    def drop_site(side, layer, kind):
+        assert side in (0, 1) and -1 <= layer < 63 and 0 <= kind < 4
+        return (side * 64 + layer + 1) * 4 + kind
+
+    def set_dropout(self, p_drop=0.0, p_act=0.0, seed=0, step=0):
+        """Probabilities of the training passes (`training` True and save=True) of this engine; `step` is the number of
+        forwards drawn so far (dropout_tick advances it on the device)."""
+        for v in (p_drop, p_act):
+            if not 0.0 <= float(v) < 1.0:
+                raise ValueError(f"dropout probability {v} outside [0, 1)")
+        self.p_drop, self.p_act, self.drop_seed = float(p_drop), float(p_act), int(seed)
+        if self.p_drop or self.p_act:
+            if not hasattr(self.ops, "dropout_fwd"):
+                raise RuntimeError(f"ops '{getattr(self.ops, 'name', self.ops)}' has no dropout kernels")
+            self.drop_state = self.ops.dropout_state(step)
+
+    def dropout_tick(self):
+        """Once per training forward (before it): the next forward draws the masks of the next step."""
+        if self.p_drop or self.p_act:
+            self.ops.dropout_tick(self.drop_state)
+
+    def _drop(self, save):
+        on = save and self.training
+        return (self.p_drop if on else 0.0), (self.p_act if on else 0.0)
+
+    def _dropout(self, u, p, site, **kw):
+        out, m = self.ops.dropout_fwd(u, p, self.drop_seed, self.drop_state, site, **kw)
+        if self.keep_masks is not None:
+            self.keep_masks[site] = m
+        return out, m
 
     # ---- helpers -------------------------------------------------------------------------------------------------
     # Row pitch of the wide activation buffers (round 5, tools/gemm_stride_probe.py): a [48000 x 5120] bf16 operand has 10 240-byte
@@ -484,6 +529,10 @@ class WhisperEngine:
         x = ops.empty((R, D), self.stream)
         _, z2 = ops.gemm(xcol2[:R], st.conv2_packed, bias=st.p["model.encoder.conv2.bias"], act=1, want_z=True,
                          residual=st.p["model.encoder.embed_positions.weight"], r_row_mod=L, round_res=True, out=x)
+        pd, _ = self._drop(save)
+        if pd:
+            x, m = self._dropout(x, pd, self.drop_site(0, -1, 0), out=x)
+            ctx.update(pd=pd, m_emb=m)
         if save:
             ctx.update(xcol1=xcol1, z1=z1, xcol2=xcol2, z2=z2)
         else:
@@ -514,6 +563,20 @@ class WhisperEngine:
         assert Rg == R or not save
         lc = {} if save else None
         rect = {}                              # (packed training pass: the rectangular q / k / v / o of this layer's attentions)
+        pd, pa = self._drop(save)
+        if pd or pa:
+            side, layer = int(enc_out is not None), int(p.rsplit(".", 1)[1])
+            lc.update(pd=pd, pa=pa)
+
+        def branch(o_, w, b, x_, kind):
+            """x + out_proj / fc2 of a residual branch; with dropout the GEMM stops at the rounded branch value and the
+            streaming kernel masks, scales and adds (lc keeps the mask)"""
+            if not pd:
+                return ops.gemm(o_[:Rg], w, bias=b, residual=x_, round_res=True, out_dtype=self.stream, out_row_pad=xp)
+            u = ops.gemm(o_[:Rg], w, bias=b)
+            y, lc[f"m{kind}"] = self._dropout(u, pd, self.drop_site(side, layer, kind), residual=x_, out_dtype=self.stream,
+                                              out_row_pad=xp)
+            return y
 
         def attend(q_src, k, v, Lkv, is_causal, cols):
             """q_src [>= R, cols] with the queries in its first D columns -> o [Rg, D]"""
@@ -565,7 +628,7 @@ class WhisperEngine:
         else:
             o, lse = attend(qkv, None, None, L, causal, 3 * D)
         xp = self.stream_row_pad // (4 if self.stream == torch.float32 else 2)
-        x1 = ops.gemm(o[:Rg], av["wo"], bias=av["bo"], residual=x, round_res=True, out_dtype=self.stream, out_row_pad=xp)
+        x1 = branch(o, av["wo"], av["bo"], x, 0)
         if save:
             lc.update(x0=x, mu0=mu, rs0=rs, h0=h, qkv=qkv, o0=o, lse0=lse)
             if live is not None:
@@ -584,7 +647,7 @@ class WhisperEngine:
                 assert live is None
                 ops.cross_attn_probs(q[:R], kv[:Re, :D], probe[0], probe[1], probe[2], B, L, Lk)
             o, lse = attend(q, kv[:Re, :D], kv[:Re, D:], Lk, False, D)
-            x1 = ops.gemm(o[:Rg], cv["wo"], bias=cv["bo"], residual=x, round_res=True, out_dtype=self.stream, out_row_pad=xp)
+            x1 = branch(o, cv["wo"], cv["bo"], x, 1)
             if save:
                 lc.update(x1=x, mu1=mu, rs1=rs, h1=h, q1=q, kv1=kv, o1=o, lse1=lse)
                 if live is not None:
@@ -597,8 +660,9 @@ class WhisperEngine:
                        want_z=("grad" if self.ffn_keeps_gelu_grad else True) if save else False, out=a[:Rg],
                        z_row_pad=self.ffn_row_pad)
         z = res[1] if save else None
-        x2 = ops.gemm(a[:Rg], st.s[f"{p}.fc2.weight"], bias=st.p[f"{p}.fc2.bias"], residual=x, round_res=True,
-                      out_dtype=self.stream, out_row_pad=xp)
+        if pa:          # in place: the masked activation is what fc2 and its weight gradient consume
+            _, lc["m3"] = self._dropout(a[:Rg], pa, self.drop_site(side, layer, 3), out=a[:Rg])
+        x2 = branch(a, st.s[f"{p}.fc2.weight"], st.p[f"{p}.fc2.bias"], x, 2)
         if save:
             lc.update(x2=x, mu2=mu, rs2=rs, h2=h, a=a, z=z)
         return x2, lc
@@ -639,6 +703,10 @@ class WhisperEngine:
             xp, x = x, ops.empty((Rg, d.d_model), self.stream)
             ops.gather_rows(xp, live.idx, x)
             del xp
+        pd, _ = self._drop(save)
+        if pd:          # (after the gather: the mask is in the row order the layers see)
+            _, m = self._dropout(x[:Rv], pd, self.drop_site(1, -1, 0), out=x[:Rv])
+            ctx.update(pd=pd, m_emb=m)
         for i in range(d.dec_layers):
             x, lc = self._layer_fwd(f"model.decoder.layers.{i}", x, B, T, enc_out, Lk, True, save, Rg,
                                     live if packed else None)
@@ -890,13 +958,30 @@ class WhisperEngine:
         """Backward of _layer_fwd.  dres: fp32 [R, D] gradient w.r.t. the layer output (updated in place to the
         gradient w.r.t. the layer input); dy: its low-precision copy, whose column sums were already added to this
         layer's fc2.bias gradient by the kernel that produced it.  denc: fp32 [Re, D] accumulator for the encoder
-        output gradient.  Returns (dres, dy_for_the_layer_below)."""
+        output gradient.  Returns (dres, dy_for_the_layer_below).
+        With dropout on the residual branches (lc["pd"]) the gradient that enters a branch is du = m . bf16(dy / (1-p)), not dy:
+        du feeds the branch's dX GEMM, its weight gradient and its bias gradient (a column sum of du), so the LayerNorm
+        backward above emits NO column sums (the callers pass colsum_to=None) and `dy` arrives without them."""
         ops, st, d = self.ops, self.st, self.dims
         D, H, Rp = d.d_model, d.heads, B * L
         R = Rp if live is None else live.n      # live (packed training pass, _layer_fwd): row-local work over the live rows, attention
                                                 # over the layer's rectangular buffers between a scatter and a gather
         tr = st.is_trainable(f"{p}.fc1.weight")
         cross = "x1" in lc
+        pd, pa = lc.get("pd", 0.0), lc.get("pa", 0.0)
+
+        def enter(dy_, kind):
+            """gradient entering residual branch `kind` (pad rows zero: the weight-gradient GEMM contracts over them)"""
+            if not pd:
+                return dy_
+            du = self.act(R, D, pad=self.row_pad)
+            ops.dropout_bwd(dy_[:R], lc[f"m{kind}"], pd, out=du[:R])
+            return du
+
+        def out_bias(name):
+            """bias gradient of a branch's output projection for _wgrad: with dropout only (else the LayerNorm backward above
+            has added it already)"""
+            return self._bias_grad(name) if pd else None
 
         def to_rect(t, cols):
             """packed rows -> a ZEROED (batch, position) rectangle (a row that is dead in this step must contribute nothing)"""
@@ -906,21 +991,25 @@ class WhisperEngine:
         # --- feed forward
         dz = self.act(R, d.ffn, pad=self.ffn_row_pad)
         # (fc1.bias gradient = column sums of dz: accumulated by this GEMM's epilogue, no separate pass over dz)
-        fuse_cs = tr and self.fuse_fc1_bias_grad and R > 64
+        fuse_cs = tr and self.fuse_fc1_bias_grad and R > 64 and not pa
+        dy = enter(dy, 2)
         ops.gemm(dy[:R], st.s[f"{p}.fc2.weight"], trans_b=True, zgrad=lc["z"], out=dz[:R],
                  colsum=st.g[f"{p}.fc1.bias"] if fuse_cs else None)
+        if pa:          # (the mask and gelu' commute; fc1.bias then comes from the masked dz through _wgrad)
+            ops.dropout_bwd(dz[:R], lc["m3"], pa, out=dz[:R])
         if tr:
-            self._wgrad(dy, lc["a"], st.g[f"{p}.fc2.weight"], None, R)
+            self._wgrad(dy, lc["a"], st.g[f"{p}.fc2.weight"], out_bias(f"{p}.fc2.bias"), R)
             self._wgrad(dz, lc["h2"], st.g[f"{p}.fc1.weight"], None if fuse_cs else st.g[f"{p}.fc1.bias"], R)
         dh = ops.gemm(dz[:R], st.s[f"{p}.fc1.weight"], trans_b=True, out_row_pad=self.dx_row_pad)
         nb = f"{p}.encoder_attn.out_proj.bias" if cross else f"{p}.self_attn.out_proj.bias"
         dres, dy = self._ln_bwd(f"{p}.final_layer_norm", dh, lc["x2"], lc["mu2"], lc["rs2"], dres, R, emit=True,
-                                colsum_to=self._bias_grad(nb))
+                                colsum_to=None if pd else self._bias_grad(nb))
         del dz, dh
         # --- cross attention
         if cross:
             cv = st.attn_views(f"{p}.encoder_attn")
             Re = B * Lk
+            dy = enter(dy, 1)
             do = ops.gemm(dy[:R], cv["wo"], trans_b=True, out_row_pad=self.dx_row_pad)
             dq = self.act(R, D, pad=self.row_pad)
             dkv = self.act(Re, 2 * D, pad=self.row_pad)
@@ -938,7 +1027,7 @@ class WhisperEngine:
                 ops.gather_rows(dq_r, live.idx, dq)
                 del do_r, dq_r
             if tr:
-                self._wgrad(dy, lc["o1"], cv["g_wo"], None, R)
+                self._wgrad(dy, lc["o1"], cv["g_wo"], out_bias(f"{p}.encoder_attn.out_proj.bias"), R)
                 self._wgrad(dq, lc["h1"], cv["g_wqkv"][:D], None if fb else cv["g_bqkv"][:D], R)
                 self._wgrad(dkv, lc["enc_out"], cv["g_wqkv"][D:], None if fb else cv["g_bqkv"][D:], Re, bias_cols=[(D, 2 * D)])
             if denc is not None:
@@ -946,10 +1035,11 @@ class WhisperEngine:
                          out_dtype=torch.float32, out=denc)
             dh = ops.gemm(dq[:R], cv["wqkv"][:D], trans_b=True, out_row_pad=self.dx_row_pad)
             dres, dy = self._ln_bwd(f"{p}.encoder_attn_layer_norm", dh, lc["x1"], lc["mu1"], lc["rs1"], dres, R,
-                                    emit=True, colsum_to=self._bias_grad(f"{p}.self_attn.out_proj.bias"))
+                                    emit=True, colsum_to=None if pd else self._bias_grad(f"{p}.self_attn.out_proj.bias"))
             del do, dq, dkv, dh
         # --- self attention
         av = st.attn_views(f"{p}.self_attn")
+        dy = enter(dy, 0)
         do = ops.gemm(dy[:R], av["wo"], trans_b=True, out_row_pad=self.dx_row_pad)
         dqkv = self.act(R, 3 * D, pad=self.row_pad)
         qkv = lc["qkv"]
@@ -968,7 +1058,7 @@ class WhisperEngine:
             ops.gather_rows(dqkv_r, live.idx, dqkv)
             del do_r, dqkv_r
         if tr:
-            self._wgrad(dy, lc["o0"], av["g_wo"], None, R)
+            self._wgrad(dy, lc["o0"], av["g_wo"], out_bias(f"{p}.self_attn.out_proj.bias"), R)
             self._wgrad(dqkv, lc["h0"], av["g_wqkv"], None if fb else av["g_bqkv"], R, bias_cols=[(0, D), (2 * D, 3 * D)])
         dh = ops.gemm(dqkv[:R], av["wqkv"], trans_b=True, out_row_pad=self.dx_row_pad)
         return self._ln_bwd(f"{p}.self_attn_layer_norm", dh, lc["x0"], lc["mu0"], lc["rs0"], dres, R, emit=emit_last,
@@ -1004,13 +1094,14 @@ class WhisperEngine:
             ops.scatter_rows(dh, live.idx, dhp)
             dh = dhp
         nl = d.dec_layers
+        pd = ctx.get("pd", 0.0)      # residual-branch dropout: the branches form their own bias gradients (_layer_bwd)
         dres, dy = self._ln_bwd("model.decoder.layer_norm", dh, ctx["x_final"], ctx["mu"], ctx["rs"], None, Rv,
-                                emit=True, colsum_to=self._bias_grad(f"model.decoder.layers.{nl - 1}.fc2.bias"))
+                                emit=True, colsum_to=None if pd else self._bias_grad(f"model.decoder.layers.{nl - 1}.fc2.bias"))
         denc = ops.zeros((B * Lk, D), torch.float32) if want_denc else None
         for i in reversed(range(nl)):
             lc = ctx["layers"][i]
             lc["enc_out"] = ctx["enc_out"]
-            below = self._bias_grad(f"model.decoder.layers.{i - 1}.fc2.bias") if i > 0 else None
+            below = self._bias_grad(f"model.decoder.layers.{i - 1}.fc2.bias") if (i > 0 and not pd) else None
             dres, dy = self._layer_bwd(f"model.decoder.layers.{i}", lc, dres, dy, B, T, Lk, True, denc, i > 0, below,
                                        live=live if packed else None)
             ctx["layers"][i] = None
@@ -1018,6 +1109,8 @@ class WhisperEngine:
         if tr_emb or st.is_trainable("model.decoder.embed_positions.weight"):
             dtok = st.g[emb] if tr_emb else self._scratch_tok()
             dpos = st.g.get("model.decoder.embed_positions.weight")
+            if pd:
+                ops.dropout_bwd(dres[:Rv], ctx["m_emb"], pd, out=dres[:Rv])
             if packed:                                        # live rows -> (batch, position); dead rows: zero
                 dres_r = ops.zeros((R, D), dres.dtype)
                 ops.scatter_rows(dres[:Rv], live.idx, dres_r)
@@ -1050,17 +1143,19 @@ class WhisperEngine:
         dyf = self.act(R, D)
         ops.cast_bf16(denc, out=dyf[:R])
         nl = d.enc_layers
+        pd = ctx.get("pd", 0.0)
         dres, dy = self._ln_bwd("model.encoder.layer_norm", dyf, ctx["x_final"], ctx["mu"], ctx["rs"], None, R,
-                                emit=True, colsum_to=self._bias_grad(f"model.encoder.layers.{nl - 1}.fc2.bias"))
+                                emit=True, colsum_to=None if pd else self._bias_grad(f"model.encoder.layers.{nl - 1}.fc2.bias"))
         for i in reversed(range(nl)):
-            below = self._bias_grad(f"model.encoder.layers.{i - 1}.fc2.bias") if i > 0 else None
+            below = self._bias_grad(f"model.encoder.layers.{i - 1}.fc2.bias") if (i > 0 and not pd) else None
             dres, dy = self._layer_bwd(f"model.encoder.layers.{i}", ctx["layers"][i], dres, dy, B, L, 0, False, None,
                                        i > 0, below)
             ctx["layers"][i] = None
             self._wgrad_fence()
             if on_ready is not None:
                 # everything above layer i-1's last parameter is final (fc2.bias of layer i-1 still receives the
-                # column sums emitted by this layer's last LayerNorm backward, so the cut is at layer i's first entry)
+                # column sums emitted by this layer's last LayerNorm backward, so the cut is at layer i's first entry; with
+                # residual-branch dropout every fc2.bias is written by its own layer's backward, and the same cut holds)
                 rng = self.param_range(f"model.encoder.layers.{i}.")
                 if rng is not None:
                     hi = self._enc_ready_hi if hasattr(self, "_enc_ready_hi") and self._enc_ready_hi else \
@@ -1069,6 +1164,8 @@ class WhisperEngine:
                     self._enc_ready_hi = rng[0]
         # conv stem: x0 = gelu(conv2(a1)) + pos ; a1 = gelu(conv1(mel))
         dz2 = self.act(R, D)
+        if pd:
+            ops.dropout_bwd(dres[:R], ctx["m_emb"], pd, out=dres[:R])
         ops.gelu_bwd(dres, ctx["z2"], out=dz2[:R])
         gw2 = ops.zeros((D, 3 * D), torch.float32)
         ops.gemm(dz2, ctx["xcol2"], trans_a=True, trans_b=True, out_dtype=torch.float32, out=gw2, atomic_acc=True)

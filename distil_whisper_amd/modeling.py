@@ -253,6 +253,22 @@ class _Model(nn.Module):
         self.decoder = _Decoder(d)
 
 
+def check_regularisers(config):
+    """`dropout` and `activation_dropout` (the row-local dropouts: embeddings, the three residual branches, the GELU output of
+    fc1) are built and apply in training mode; the other regularisers of `transformers.WhisperConfig` are not."""
+    for k in ("dropout", "activation_dropout"):
+        v = getattr(config, k, 0.0) or 0.0
+        if not 0.0 <= float(v) < 1.0:
+            raise ValueError(f"{k}={v}: a probability in [0, 1) is expected")
+    bad = [k for k in ("attention_dropout", "encoder_layerdrop", "decoder_layerdrop") if getattr(config, k, 0.0)]
+    if getattr(config, "scale_embedding", False):
+        bad.append("scale_embedding")
+    if bad:
+        raise ValueError(f"{', '.join(bad)}: not implemented on the MI355X path, which builds `dropout` and `activation_dropout` "
+                         "only (attention_dropout needs the mask inside the flash-attention kernels, layerdrop changes the "
+                         "launch sequence of a captured step; scale_embedding is False in every Whisper config)")
+
+
 class WhisperConfig:
     """The fields of `transformers.WhisperConfig` this path reads (TF:configuration_whisper.py:127-164), loadable from
     and writable to a checkpoint directory's config.json.  A `transformers.WhisperConfig` works in its place."""
@@ -277,10 +293,7 @@ class WhisperConfig:
             raise ValueError("the HIP attention kernel implements head_dim 64 (every Whisper checkpoint)")
         if self.activation_function != "gelu":
             raise ValueError("the HIP GEMM epilogue implements Whisper's exact GELU")
-        if any(getattr(self, k) for k in ("dropout", "attention_dropout", "activation_dropout", "encoder_layerdrop",
-                                          "decoder_layerdrop")) or self.scale_embedding:
-            raise ValueError("dropout / layerdrop / scale_embedding are 0 / False in every Whisper config; the MI355X "
-                             "path does not implement them")
+        check_regularisers(self)
 
     def to_dict(self):
         d = {k: v for k, v in vars(self).items() if not k.startswith("_")}
@@ -416,6 +429,9 @@ class _EngineFn(torch.autograd.Function):
         train = any(ctx.needs_input_grad[5:])  # (grad mode is off inside Function.forward; this is the real signal)
         enc_train = train and model._encoder_requires_grad()
         ectx = None
+        eng.training = bool(train and model.training)
+        if eng.training:
+            eng.dropout_tick()          # this forward draws the masks of the next step (nothing happens with both probabilities 0)
         if enc_in is None:
             enc, ectx = eng.encode(input_features.to(torch.float32).contiguous(), save=enc_train)
         else:
@@ -537,8 +553,9 @@ class WhisperForConditionalGeneration(nn.Module):
     skip_dead_positions = os.environ.get("DW_SKIP_DEAD_POSITIONS", "0") not in ("", "0", "false", "False")
 
     def __init__(self, config, ops=None, device="cuda:0", state_dict=None, seed=0, frozen_prefixes=(),
-                 dtype=torch.float32):
+                 dtype=torch.float32, dropout_seed=0):
         super().__init__()
+        check_regularisers(config)
         self.config = config
         self.dims = WhisperDims.from_any(config)
         self.ops = ops if ops is not None else _default_ops(device)
@@ -550,6 +567,11 @@ class WhisperForConditionalGeneration(nn.Module):
         self.store = ParamStore(self.ops, self.dims, sd, trainable=not pure_bf16,
                                 frozen_prefixes=tuple(frozen_prefixes), round_bf16=pure_bf16)
         self.engine = WhisperEngine(self.ops, self.store, self.ops.lowp if pure_bf16 else torch.float32)
+        # `config.dropout` / `config.activation_dropout` apply to training-mode forwards that keep activations (module.train(),
+        # parameters that require grad), as in the reference's layers; the inference-only bf16 model ignores them
+        p_drop, p_act = float(getattr(config, "dropout", 0.0) or 0.0), float(getattr(config, "activation_dropout", 0.0) or 0.0)
+        if not pure_bf16 and (p_drop or p_act):
+            self.engine.set_dropout(p_drop, p_act, seed=dropout_seed)
         self._decoders = {}
         self.model = _Model(self.dims)
         self.proj_out = nn.Linear(self.dims.d_model, self.dims.vocab, bias=False, device="meta")

@@ -108,6 +108,11 @@ _SIGS = {
                           C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "dw_dtw": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                 C.c_void_p], C.c_int),
+    "dw_dropout_fwd": ([C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                        C.c_int, C.c_int, C.c_uint32, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "dw_dropout_bwd": ([C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float,
+                        C.c_void_p], C.c_int),
+    "dw_dropout_tick": ([C.c_void_p, C.c_void_p], C.c_int),
     "dw_score_tokens": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                          C.c_void_p, C.c_void_p], C.c_int),
@@ -140,6 +145,11 @@ def _dt(t):
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def dropout_threshold(p):
+    """An element is kept iff its 32-bit random word >= this (include/dwamd.h dw_dropout_fwd)."""
+    return min(2**32 - 1, int(round(float(p) * 2.0**32)))
 
 
 def _rup4(x):
@@ -715,6 +725,45 @@ class HipOps:
                                            self._stream()), "score_tokens")
         return (None if scores is None else scores[:, :, :V]), chosen, logprob
 
+    # ---- training-mode dropout (csrc/dropout.hip; TF:modeling_whisper.py:398-406, 479-502, 625, 763) ------------------------
+    def dropout_state(self, step=0):
+        """The 64-bit step counter of the mask generator, resident on the device (include/dwamd.h dw_dropout_tick)."""
+        return torch.tensor([int(step)], dtype=torch.int64, device=self.device)
+
+    def dropout_tick(self, state):
+        assert state.dtype == torch.int64 and state.numel() == 1
+        self._chk(self.lib.dw_dropout_tick(_p(state), self._stream()), "dropout_tick")
+
+    def dropout_fwd(self, u, p, seed, state, site, residual=None, out=None, out_dtype=None, out_row_pad=0):
+        """out = residual + m * (u * 1/(1-p)) (the product rounded to bf16 when u is bf16); residual may be None, `out` may be
+        `u` or `residual`.  2-D operands with unit column stride, any row pitch.  -> (out, mask uint8 [rows, cols / 8])."""
+        rows, cols = u.shape
+        assert u.stride(1) == 1 and cols % 8 == 0 and 0.0 <= p < 1.0
+        if out is None:
+            out = self.empty((rows, cols + out_row_pad), u.dtype if out_dtype is None else out_dtype)
+            if out_row_pad:
+                out = out[:, :cols]
+        assert out.shape == (rows, cols) and out.stride(1) == 1
+        assert residual is None or (residual.shape[1] == cols and residual.shape[0] >= rows and residual.stride(1) == 1)
+        assert state.dtype == torch.int64 and state.numel() == 1
+        mask = self.empty((rows, cols // 8), torch.uint8)
+        self._chk(self.lib.dw_dropout_fwd(_p(u), _dt(u), u.stride(0), _p(residual), _dt(residual) if residual is not None else 0,
+                                          residual.stride(0) if residual is not None else 0, _p(out), _dt(out), out.stride(0),
+                                          _p(mask), rows, cols, dropout_threshold(p), 1.0 / (1.0 - p), int(seed) & (2**64 - 1),
+                                          int(site), _p(state), self._stream()), "dropout_fwd")
+        return out, mask
+
+    def dropout_bwd(self, dy, mask, p, out=None):
+        """out = m * (dy * 1/(1-p)) (rounded to bf16 when dy is bf16); `out` may be `dy`."""
+        rows, cols = dy.shape
+        assert dy.stride(1) == 1 and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.shape == (rows, cols // 8)
+        if out is None:
+            out = self.empty((rows, cols), dy.dtype)
+        assert out.shape == (rows, cols) and out.stride(1) == 1
+        self._chk(self.lib.dw_dropout_bwd(_p(dy), _dt(dy), dy.stride(0), _p(mask), _p(out), _dt(out), out.stride(0), rows, cols,
+                                          1.0 / (1.0 - p), self._stream()), "dropout_bwd")
+        return out
+
     def adamw(self, p, g, m, v, shadow, sumsq, max_norm, grad_mul, lr, beta1, beta2, eps, weight_decay, step):
         assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
         self._chk(self.lib.dw_adamw(_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), _p(sumsq), float(max_norm),
@@ -754,5 +803,6 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),
                     ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("greedy_select_history", "select"),
                     ("cross_attn_probs", "align"),
-                    ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score")):
+                    ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score"), ("dropout_fwd", "dropout_fwd"),
+                    ("dropout_bwd", "dropout_bwd")):
     setattr(HipOps, _name, _timed(_key)(getattr(HipOps, _name)))

@@ -246,6 +246,25 @@ int dw_adam_tick(double* state, const float* gate, void* stream);
 int dw_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, const float* sumsq,
                  float max_norm, float grad_mul, const double* state, double eps, double weight_decay, void* stream);
 
+/* ---- a10b: training-mode dropout of the student ------------------------------------------------------------------
+ * Replaces nn.functional.dropout at the row-local sites of TF:modeling_whisper.py: the embeddings (WhisperEncoder.forward
+ * 625, WhisperDecoder.forward 763: `dropout`), the three residual branches of a layer (WhisperEncoderLayer 398 / 406,
+ * WhisperDecoderLayer 479 / 493 / 502: `dropout`) and the GELU output of fc1 (404 / 500: `activation_dropout`); run_distillation.py sets them on the student config (the `--dropout` family of the Flax recipe).
+ * Mask: one bit per element, byte b of row r covers columns 8b .. 8b+7 (bit j = column 8b+j), row pitch cols/8 bytes;
+ * cols %% 8 == 0.  Element e = row*cols + col keeps its value iff word (e & 3) of Philox4x32-10(counter = (e >> 2, site,
+ * step_lo, step_hi), key = seed) >= thr, thr = min(2^32-1, round(p * 2^32)); rows*cols < 2^34 (else DW_EUNSUP).  `step` is
+ * a 64-bit counter in DEVICE memory (dw_dropout_tick advances it), so a replayed HIP graph draws fresh masks.
+ * dw_dropout_fwd: out = residual + m * t with t = u * scale, rounded to bf16 when u is bf16 (scale = 1/(1-p)); residual
+ *   may be NULL; u / residual / out are bf16 or f32 with row pitches ldu / ldr / ldo in elements (16-byte aligned rows);
+ *   out may alias u or residual (same dtype and pitch: every element is read and written by the same lane); mask is written.
+ * dw_dropout_bwd: out = m * t with t = dy * scale, rounded to bf16 when dy is bf16; reads the mask; may run in place. */
+int dw_dropout_fwd(const void* u, int u_dtype, int64_t ldu, const void* residual, int r_dtype, int64_t ldr, void* out,
+                   int out_dtype, int64_t ldo, uint8_t* mask, int rows, int cols, uint32_t thr, float scale, uint64_t seed,
+                   int site, const uint64_t* step, void* stream);
+int dw_dropout_bwd(const void* dy, int dy_dtype, int64_t lddy, const uint8_t* mask, void* out, int out_dtype, int64_t ldo,
+                   int rows, int cols, float scale, void* stream);
+int dw_dropout_tick(uint64_t* step, void* stream);
+
 /* ---- a11: token selection of one greedy-decoding step for the whole batch (TF:generation/logits_process.py processors
  * MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens, WhisperTimeStamp as installed by
  * TF:models/whisper/generation_whisper.py:1774-1812, then argmax and the EOS / pad bookkeeping of GenerationMixin).
