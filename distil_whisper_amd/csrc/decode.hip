@@ -13,6 +13,9 @@
 // HBM-bound: B x V x 2 bytes read once (twice in timestamp mode; the row is L2 resident).  One 1024-thread workgroup
 // per row; being a plain kernel on the launch stream it is captured into the per-position HIP graphs like the rest of
 // the step (the torch implementation of the timestamp rules was not graph-safe).
+// Sampling (dw_sample_select, further down) is the same launch with the warpers and the multinomial draw behind the rules:
+// TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper (TF:logits_process.py, in TF:utils.py `_get_logits_processor`'s
+// order), `softmax` + `torch.multinomial` of TF:utils.py `_sample`, as reached from run_eval.py:690-739 (temperature fallback).
 #include "common.h"
 #include "../../include/dwamd.h"
 
@@ -275,6 +278,414 @@ extern "C" int dw_greedy_select_history(const void* logits, int B, int V, int64_
     hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V,
                        (long)ld, suppress, begin_suppress, first, no_eos, forced, ts_begin, max_initial, tokens,
                        (long)tok_ld, n, begin_index, eos, fill, done, cur, repetition_penalty, no_repeat_ngram);
+    DW_CHECK_LAUNCH();
+    return DW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Sampled selection (dw_sample_select): `generate(do_sample=True, temperature=, top_k=, top_p=)` in the same single launch.
+// Reference behaviour: TF:generation/utils.py `_get_logits_processor` (processors, then TemperatureLogitsWarper, TopKLogitsWarper,
+// TopPLogitsWarper of TF:generation/logits_process.py, in that order) and `_sample` (`probs = softmax(scores)`,
+// `torch.multinomial(probs, 1)`), as reached from run_eval.py:690-739 (`temperature=(0.0, 0.2, ..., 1.0)` fallback passes,
+// TF:generation_whisper.py `generate_with_fallback`).
+// For one draw per row torch.multinomial IS `argmax(probs / q)` with q = empty_like(probs).exponential_(1): the caller draws q
+// (`noise`) with torch's generator, so the token is the reference's; everything else happens here.
+//   1. the processed fp32 score of every column as greedy_select_kernel<true> judges it (excluded = -inf), mass rule included;
+//   2. s / temperature, correctly rounded like the reference's IEEE division;
+//   3. top-k: the k-th largest of all V scores by a radix select, columns with s < kth removed (ties stay);
+//   4. top-p: a column is removed iff the probability of all columns with a score <= its own is <= 1 - top_p.  The reference
+//      removes a prefix of an ascending sort, so it splits the group of equal scores that straddles the boundary in the order
+//      its sort happens to give; this kernel keeps that group whole (a documented deviation);
+//   5. the winner is argmax exp(s - max) / noise over the surviving columns, equal quotients to the smaller column (softmax's
+//      common factor 1 / sum does not move the argmax);
+//   6. EOS bookkeeping as in the greedy kernel.
+// The row's scores stay in registers (NCH chunks of four columns per thread: 13 up to 53 248 columns, 16 up to 65 536).
+// Both thresholds come from ONE search, `select_key`: the smallest 32-bit key K whose cumulative weight W(<= K) exceeds T, found
+// eight bits at a time over a 256-bin LDS histogram of 64-bit integers.  Top-k: key = ~order(s), weight 1, T = k - 1.  Top-p: key
+// = order(s), weight = exp(s - max) in 2^-32 fixed point, T = floor((1 - top_p) * Z).  Integer sums do not depend on the order
+// of the adds, so no threshold depends on the arrival order of an atomic and equal inputs give equal tokens.  (Fixed point,
+// rounded to nearest: 65 536 roundings of at most 2^-33 each sum to less than 8e-6 of the largest column's weight even if all
+// fell the same way, and to ~2e-8 as the random walk they are; the fast exponential's own error is of the order 1e-7 relative.)
+// LDS adds to one bin serialise, and the first digit of fp32 scores fills a handful of bins, so the searches first narrow the
+// candidates with the per-thread extrema: the k-th largest of the 1024 thread maxima is a lower bound of the k-th largest score
+// (k <= 1024); for top-p the 256-th largest thread maximum L is used when the mass below L fits into the budget (a peaked
+// distribution, the usual case).  Otherwise every finite column is a candidate: correct, slower.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned order_key(float v) {         // unsigned order == float order; -0 counts as +0
+    const unsigned u = __float_as_uint(v + 0.0f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+#define KEY_NEG_INF 0x007fffffu                                  // order_key(-inf): every finite score has a larger key
+
+typedef unsigned long long u64;
+struct SelScratch { u64 hist[256]; u64 wtot[4]; u64 base; unsigned digit; u64 red[SEL_NT / 64]; };
+
+__device__ __forceinline__ u64 block_sum_u64(u64 x, u64* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    u64 t = 0;
+    for (int i = 0; i < SEL_NT / 64; ++i) t += red[i];
+    return t;
+}
+
+// The smallest key K among the thread block's items with base + W(items <= K) > T.  `each(f)` calls f(key, weight) for every item
+// of the calling thread; the caller guarantees base <= T < base + W(all items).
+template <class Each>
+__device__ __forceinline__ unsigned select_key(Each&& each, u64 base, u64 T, SelScratch* sc) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    unsigned prefix = 0;
+#pragma unroll 1
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        const unsigned pmask = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+        __syncthreads();
+        if (tid < 256) sc->hist[tid] = 0;
+        __syncthreads();
+        each([&](unsigned key, u64 w) {
+            if ((key & pmask) == prefix) atomicAdd(&sc->hist[(key >> shift) & 255u], w);
+        });
+        __syncthreads();
+        u64 own = 0, incl = 0;
+        if (tid < 256) {                           // inclusive scan of the 256 bins: within a wave, then across the four waves
+            own = incl = sc->hist[tid];
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const u64 y = __shfl_up(incl, o);
+                if (lane >= o) incl += y;
+            }
+            if (lane == 63) sc->wtot[tid >> 6] = incl;
+        }
+        __syncthreads();
+        if (tid < 256) {
+            for (int w = 0; w < (tid >> 6); ++w) incl += sc->wtot[w];
+            const u64 before = base + incl - own;
+            if (before <= T && before + own > T) { sc->digit = (unsigned)tid; sc->base = before; }   // exactly one bin
+        }
+        __syncthreads();
+        prefix |= sc->digit << shift;
+        base = sc->base;
+    }
+    return prefix;
+}
+
+template <int NCH>
+__global__ __launch_bounds__(SEL_NT) void sample_select_kernel(
+    const bf16* logits, int V, long ld, const uint8_t* suppress, const uint8_t* begin_suppress, int first, int no_eos,
+    int tb, int max_initial, int64_t* tokens, long tok_ld, int n, int begin_index, int eos, int fill,
+    uint8_t* done, int64_t* cur, float rep_pen, int ngram, float temperature, int top_k, float top_p, const float* noise,
+    long noise_ld) {
+    __shared__ Best red[SEL_NT / 64];
+    __shared__ float redf[SEL_NT / 64];
+    __shared__ int redi[SEL_NT / 64];
+    __shared__ unsigned seen[SEL_HIST_V / 32], banned[SEL_HIST_V / 32];
+    __shared__ SelScratch sc;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int64_t* row_tok = tokens + (long)b * tok_ld;
+    if (eos >= 0 && done[b]) {                     // a finished row takes `fill` whatever its logits say
+        if (tid == 0) { row_tok[n] = fill; cur[b] = fill; if (fill == eos) done[b] = 1; }
+        return;
+    }
+    const bf16* row = logits + (long)b * ld;
+    // ---- history bitmaps and the row state of the timestamp rules: as in greedy_select_kernel<true> ----
+    for (int w = tid; w < SEL_HIST_V / 32; w += SEL_NT) { seen[w] = 0u; banned[w] = 0u; }
+    __syncthreads();
+    {
+        const int g = ngram;
+        for (int i = tid; i < n; i += SEL_NT) {
+            const long t = row_tok[i];
+            if (t < 0 || t >= V) continue;
+            const unsigned bit = 1u << ((int)t & 31);
+            if (rep_pen != 1.0f) atomicOr(&seen[(int)t >> 5], bit);
+            if (g > 0 && i >= g - 1) {
+                bool hit = true;
+                for (int k = 1; k < g && hit; ++k) hit = row_tok[i - k] == row_tok[n - k];
+                if (hit) atomicOr(&banned[(int)t >> 5], bit);
+            }
+        }
+    }
+    __syncthreads();
+    auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
+    const bool ts_mode = tb >= 0;
+    const int tsb = ts_mode ? tb : V + 1;
+    bool last_ts = false, pen_ts = true, any_ts = false;
+    int ts_last = 0;
+    const int L = n - begin_index;
+    if (ts_mode && L >= 1) {
+        last_ts = row_tok[n - 1] >= tsb;
+        pen_ts = L >= 2 ? row_tok[n - 2] >= tsb : true;
+        int pos = 0;
+        for (int i = tid; i < L; i += SEL_NT) pos = row_tok[begin_index + i] >= tsb ? max(pos, i + 1) : pos;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pos = max(pos, __shfl_xor(pos, o));
+        if ((tid & 63) == 0) redi[tid >> 6] = pos;
+        __syncthreads();
+        pos = 0;
+        for (int i = 0; i < SEL_NT / 64; ++i) pos = max(pos, redi[i]);
+        any_ts = pos > 0;
+        if (any_ts) {
+            const int last_val = (int)row_tok[begin_index + pos - 1];
+            ts_last = (last_ts && !pen_ts) ? last_val : last_val + 1;
+        }
+    }
+    int tlo = 0, thi = ts_mode ? tsb : V, slo = V, shi = V;
+    const int ban_eos = no_eos ? eos : -1, ban_nots = ts_mode ? tsb - 1 : -1;
+    if (ts_mode) {
+        if (L >= 1) {
+            if (last_ts && pen_ts) { slo = shi = V; }
+            else {
+                slo = any_ts ? max(tsb, ts_last) : tsb;
+                if (last_ts) tlo = eos;
+            }
+        } else {
+            tlo = thi = 0;
+            slo = tsb;
+            shi = max_initial >= 0 ? min(V, tsb + max_initial + 1) : V;
+        }
+    }
+    // ---- 1. processed scores into registers: slot 4 i + e holds column tid * 4 + i * 4096 + e (-inf: excluded or beyond V) ----
+    const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
+    auto masks_of = [&](int c0) -> unsigned {
+        unsigned mask = 0;
+        if (word_masks && c0 + 3 < V) {
+            if (suppress) mask |= *(const unsigned*)(suppress + c0);
+            if (first && begin_suppress) mask |= *(const unsigned*)(begin_suppress + c0);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c0 + e < V && ((suppress && suppress[c0 + e]) || (first && begin_suppress && begin_suppress[c0 + e])))
+                    mask |= 0xffu << (8 * e);
+        }
+        return mask;
+    };
+    float s[NCH * 4];
+    float btv = -INFINITY, bsv = -INFINITY;            // best allowed text / timestamp score (mass rule)
+    {
+        const int clast = (V - 1) & ~3;
+        bf16x4 xr[NCH];
+        unsigned mr[NCH];
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int c0 = min(tid * 4 + i * SEL_NT * 4, clast);
+            xr[i] = *(const bf16x4*)(row + c0);
+            mr[i] = masks_of(c0);
+        }
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int c0 = tid * 4 + i * SEL_NT * 4, c3 = c0 + 3;
+            const bool live = c0 < V;
+            const unsigned mask = mr[i];
+            const bool in_text = c0 >= tlo && c3 < thi, in_ts = c0 >= slo && c3 < shi;
+            unsigned sbits = 0, bbits = 0;
+            if (live) {
+                sbits = (seen[c0 >> 5] >> (c0 & 31)) & 0xfu;
+                bbits = (banned[c0 >> 5] >> (c0 & 31)) & 0xfu;
+            }
+            const bool clean = live && mask == 0 && c3 < V && (in_text || in_ts) && !(ban_eos >= c0 && ban_eos <= c3) &&
+                               !(ban_nots >= c0 && ban_nots <= c3) && (sbits | bbits) == 0;
+            if (clean) {                               // the whole chunk inside one allowed interval, nothing masked or penalised
+                float m = -INFINITY;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { s[4 * i + e] = bf2f(xr[i][e]); m = fmaxf(m, s[4 * i + e]); }
+                if (in_text) btv = fmaxf(btv, m); else bsv = fmaxf(bsv, m);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int c = c0 + e;
+                    const bool ok = live && c < V && !((mask >> (8 * e)) & 0xffu) &&
+                                    ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots &&
+                                    !((bbits >> e) & 1u);
+                    float v = bf2f(xr[i][e]);
+                    if ((sbits >> e) & 1u) v = penal(v);
+                    v = ok ? v : -INFINITY;
+                    s[4 * i + e] = v;
+                    if (c < tsb) btv = fmaxf(btv, v); else bsv = fmaxf(bsv, v);
+                }
+            }
+        }
+    }
+    // slot j holds column tid4 + off(j); a compare of that column with a uniform bound is written tid4 < bound - off(j), so that
+    // no loop keeps 52 column numbers in registers
+    const int tid4 = tid * 4;
+    auto off = [](int j) -> int { return (j >> 2) * (SEL_NT * 4) + (j & 3); };
+    // (a loop that compares its columns with a uniform bound takes its own copy of the bound through an empty asm: shared, or
+    // hoisted out of the passes of a search, the 52 compare results would stay live in scalar registers and spill)
+    auto fresh = [](auto x) { asm volatile("" : "+v"(x)); return x; };
+    auto block_max = [&](float x) -> float {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
+        __syncthreads();
+        if ((tid & 63) == 0) redf[tid >> 6] = x;
+        __syncthreads();
+        float t = redf[0];
+        for (int i = 1; i < SEL_NT / 64; ++i) t = fmaxf(t, redf[i]);
+        return t;
+    };
+    btv = block_max(btv);
+    bsv = block_max(bsv);
+    // the timestamp mass rule, as the greedy kernel decides it
+    bool text_out = false;
+    if (ts_mode && bsv > -INFINITY) {
+        float sum = 0.f;
+        const int t0 = fresh(tsb);
+#pragma unroll
+        for (int j = 0; j < NCH * 4; ++j)
+            if (tid4 >= t0 - off(j) && s[j] > -INFINITY) sum += __expf(s[j] - bsv);
+        sum = wave_sum(sum);
+        __syncthreads();
+        if ((tid & 63) == 0) redf[tid >> 6] = sum;
+        __syncthreads();
+        sum = 0.f;
+        for (int i = 0; i < SEL_NT / 64; ++i) sum += redf[i];
+        text_out = bsv + __logf(sum) > btv;
+    }
+    // ---- 2. temperature: s / temperature correctly rounded, as one double product per column.  (The product of s and the
+    // double reciprocal is within 2^-52 of the quotient, and a quotient of two floats keeps 2^-50 from every rounding boundary
+    // of fp32.)  From here on a score lives as its order key: integer compares, -0 and +0 share a key. ----
+    const double rtemp = 1.0 / (double)temperature;
+    const float smax = (float)((double)(text_out ? bsv : fmaxf(btv, bsv)) * rtemp);     // (rounding is monotone: the row's maximum)
+    unsigned ky[NCH * 4];
+    {
+        const int t0 = text_out ? fresh(tsb) : 0;                                       // text columns: below t0
+#pragma unroll
+        for (int j = 0; j < NCH * 4; ++j) {
+            ky[j] = tid4 < t0 - off(j) ? KEY_NEG_INF : order_key((float)((double)s[j] * rtemp));
+            if ((j & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    Best pick = {-INFINITY, 0x7fffffff};
+    if (smax > -INFINITY) {                        // (uniform: a row with no allowed column yields 0)
+        // the m-th largest of the per-thread maxima, or 0 when fewer than m threads hold a finite score
+        auto mth_thread_max = [&](int m) -> unsigned {
+            unsigned mk = 0;
+#pragma unroll
+            for (int j = 0; j < NCH * 4; ++j) mk = max(mk, ky[j]);
+            const bool fin = mk > KEY_NEG_INF;
+            if (m > SEL_NT || (int)block_sum_u64(fin ? 1 : 0, sc.red) < m) return 0u;
+            return ~select_key([&](auto&& f) { if (fin) f(~mk, (u64)1); }, 0, (u64)(m - 1), &sc);
+        };
+        // ---- 3. top-k: the k-th largest score = the k-th smallest of the inverted keys ----
+        if (top_k > 0) {
+            const int k = min(top_k, V);
+            int nfin = 0;
+#pragma unroll
+            for (int j = 0; j < NCH * 4; ++j) nfin += ky[j] > KEY_NEG_INF;
+            if ((int)block_sum_u64((u64)nfin, sc.red) >= k) {       // (fewer than k finite scores: the k-th is -inf, nothing goes)
+                unsigned lo = mth_thread_max(k);                       // candidates: finite scores with a key >= lo
+                if (!lo) lo = KEY_NEG_INF + 1u;
+                const unsigned kth = ~select_key([&](auto&& f) {
+                    const unsigned l = fresh(lo), ones = fresh(0xffffffffu);
+#pragma unroll
+                    for (int j = 0; j < NCH * 4; ++j)
+                        if (ky[j] >= l) f(ky[j] ^ ones, (u64)1);
+                }, 0, (u64)(k - 1), &sc);
+#pragma unroll
+                for (int j = 0; j < NCH * 4; ++j) ky[j] = ky[j] < kth ? KEY_NEG_INF : ky[j];
+            }
+        }
+        // ---- 4. top-p ----
+        if (top_p < 1.0f) {
+            // exp(s - max) in 2^-32 fixed point, rounded to nearest (-inf: 0; the maximum: 2^32 - 256, the largest float below
+            // 2^32).  `zero` is a 0 the compiler cannot see through (`fresh`): every pass recomputes the weights, which hoisted
+            // out of the passes would be 104 registers.
+            auto weight = [&](unsigned key, float mx, unsigned zero) -> u64 {
+                return (u64)(unsigned)__fmaf_rn(__expf(key_value(key ^ zero) - mx), 4294967040.0f, 0.5f);
+            };
+            unsigned lo = mth_thread_max(256);
+            if (!lo) lo = KEY_NEG_INF + 1u;
+            u64 Z, below;
+            {
+                const float mx = fresh(smax);
+                const unsigned l = fresh(lo), zero = fresh(0u);
+                u64 zt = 0, bl = 0;
+#pragma unroll
+                for (int j = 0; j < NCH * 4; ++j) {
+                    const u64 w = weight(ky[j], mx, zero);
+                    zt += w;
+                    bl += ky[j] < l ? w : (u64)0;
+                }
+                Z = block_sum_u64(zt, sc.red);      // >= 2^32 - 256: the maximum weighs exp(0)
+                below = block_sum_u64(bl, sc.red);
+            }
+            u64 R = (u64)((1.0 - (double)top_p) * (double)Z);
+            R = R < Z - 1 ? R : Z - 1;              // (top_p > 0: the largest column always stays)
+            if (below > R) { lo = KEY_NEG_INF + 1u; below = 0; }       // a flat distribution: every finite column is a candidate
+            const unsigned cut = select_key([&](auto&& f) {           // the smallest score that stays
+                const float mx = fresh(smax);
+                const unsigned l = fresh(lo), zero = fresh(0u);
+#pragma unroll
+                for (int j = 0; j < NCH * 4; ++j)
+                    if (ky[j] >= l) f(ky[j], weight(ky[j], mx, zero));
+            }, below, R, &sc);
+#pragma unroll
+            for (int j = 0; j < NCH * 4; ++j) ky[j] = ky[j] < cut ? KEY_NEG_INF : ky[j];
+        }
+        // ---- 5. the draw: argmax exp(s - max) / noise.  (The reference divides softmax(s) by the noise; the common factor
+        // 1 / sum does not move the argmax and is left out.)  The noise arrives in groups of four chunks, the next group
+        // requested before this one is used; addresses are clamped instead of branched around. ----
+        const float* nrow = noise + (long)b * noise_ld;
+        const unsigned zero = fresh(0u);
+        constexpr int G = 4, NG = (NCH + G - 1) / G;
+        float q[2][G * 4];
+        auto request = [&](int g, float* qb) {
+#pragma unroll
+            for (int u = 0; u < G; ++u) {
+                if (g * G + u >= NCH) break;
+                const int c0 = tid * 4 + (g * G + u) * SEL_NT * 4;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) qb[4 * u + e] = nrow[min(c0 + e, V - 1)];
+            }
+        };
+        request(0, q[0]);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g + 1 < NG) request(g + 1, q[(g + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < G; ++u) {
+                if (g * G + u >= NCH) break;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const unsigned key = ky[4 * (g * G + u) + e];
+                    const float r = __fdividef(__expf(key_value(key ^ zero) - smax), q[g & 1][4 * u + e]);
+                    if (key > KEY_NEG_INF && r > pick.v) { pick.v = r; pick.i = 4 * (g * G + u) + e; }   // (ascending: the first of equals)
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (pick.i != 0x7fffffff) pick.i = tid4 + off(pick.i);          // slot -> column
+    }
+    pick = block_best(pick, red);
+    if (tid == 0) {
+        long nxt = pick.i == 0x7fffffff ? 0 : pick.i;
+        if (eos >= 0 && nxt == eos) done[b] = 1;
+        row_tok[n] = nxt;
+        cur[b] = nxt;
+    }
+}
+
+extern "C" int dw_sample_select(const void* logits, int B, int V, int64_t ld, const uint8_t* suppress,
+                                const uint8_t* begin_suppress, int first, int no_eos, int ts_begin, int max_initial,
+                                int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, int fill, uint8_t* done,
+                                int64_t* cur, float repetition_penalty, int no_repeat_ngram, float temperature, int top_k,
+                                float top_p, const float* noise, int64_t noise_ld, void* stream) {
+    DW_CLEAR_ERR();
+    if (!tokens || !cur || B <= 0 || n < 1 || n >= tok_ld) return DW_EINVAL;
+    if (!(repetition_penalty > 0.f) || !(repetition_penalty <= 3.402823466e38f) || no_repeat_ngram < 0) return DW_EINVAL;
+    if (!logits || V <= 0 || V > SEL_HIST_V || ld < V || (ld & 3) || ((uintptr_t)logits & 7)) return DW_EINVAL;
+    if (eos >= 0 && !done) return DW_EINVAL;
+    if (ts_begin >= 0 && (eos < 0 || begin_index < 1 || begin_index > n)) return DW_EINVAL;
+    if (!(temperature > 0.f) || !(temperature <= 3.402823466e38f) || top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f))
+        return DW_EINVAL;
+    if (!noise || noise_ld < V || ((uintptr_t)noise & 3)) return DW_EINVAL;
+    auto kern = V <= 13 * SEL_NT * 4 ? sample_select_kernel<13> : sample_select_kernel<16>;
+    hipLaunchKernelGGL(kern, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V, (long)ld, suppress,
+                       begin_suppress, first, no_eos, ts_begin, max_initial, tokens, (long)tok_ld, n, begin_index, eos, fill,
+                       done, cur, repetition_penalty, no_repeat_ngram, temperature, top_k, top_p, noise, (long)noise_ld);
     DW_CHECK_LAUNCH();
     return DW_OK;
 }

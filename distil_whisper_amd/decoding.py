@@ -10,7 +10,13 @@ launch-latency bound when driven from Python.  Every token position t has fixed 
 embedding row t), so the step for position t is captured once into a HIP graph and replayed for every later batch of
 chunks; all tensors the graphs touch (current ids, token matrix, done flags, K/V caches) are allocated once.
 """
+import os
+
 import torch
+
+# DW_SAMPLE_TORCH=1 (read when a decoder is built): sampling stays on the torch ops of `_select_soft` on every engine, as on ops
+# without `sample_select` -- the A/B leg of tools/bench_sample_select.py and the reference leg of tests/test_sample_select_gpu.py
+SAMPLE_TORCH_ENV = "DW_SAMPLE_TORCH"
 
 
 def apply_timestamp_rules(scores, tokens, n, begin_index, no_timestamps_token_id, eos_token_id,
@@ -136,16 +142,29 @@ class GreedyDecoder:
         # temperature / top-k / top-p warpers and the multinomial draw).
         # Without sampling the two history rules run inside the selection kernel (dw_greedy_select_history: the history is the
         # `tokens` buffer the kernel reads anyway, so the step stays one launch and is captured into the per-position graphs
-        # like the plain one).  With sampling -- whose parity with the reference rests on torch.multinomial -- or on ops
-        # without that entry (the torch restatement oracle.ref_ops) the selection runs as torch ops on the step's logits,
-        # eagerly, without HIP-graph replay.
+        # like the plain one).  Sampling runs inside the selection kernel as well (dw_sample_select: processors, warpers and the
+        # draw in one launch, captured like the others).  For one draw per row `torch.multinomial(probs, 1, generator=g)` is
+        # `argmax(probs / q)` with `q = empty_like(probs).exponential_(1, generator=g)` on every device, so the only torch op
+        # left is that `exponential_` into the static `noise` buffer [B, V] -- the shape of `probs`, so the generator advances as
+        # on the torch path --, launched in front of every replay: outside the graph, hence no graph-safe generator registration.
+        # On ops without these entries (the torch restatement oracle.ref_ops), or with DW_SAMPLE_TORCH=1 for sampling, the
+        # selection runs as torch ops on the step's logits, eagerly, without HIP-graph replay.
+        # Generator state: both paths draw once per generated position and leave the loop at the same `check_every` boundary, so
+        # they consume the generator identically; nothing has to be restored.
         self.soft = soft
         self.history = None
+        self.sample = None
+        self.noise = None
         if soft is not None:
             rp, ng = soft.get("repetition_penalty"), int(soft.get("no_repeat_ngram_size") or 0)
             rp = 1.0 if rp is None else float(rp)
             if not soft.get("do_sample") and (rp != 1.0 or ng) and hasattr(engine.ops, "greedy_select_history"):
                 self.history = dict(repetition_penalty=rp, no_repeat_ngram=ng)
+            elif soft.get("do_sample") and hasattr(engine.ops, "sample_select") and os.environ.get(SAMPLE_TORCH_ENV, "0") in ("", "0"):
+                t, k, p = soft.get("temperature"), soft.get("top_k"), soft.get("top_p")
+                self.sample = dict(repetition_penalty=rp, no_repeat_ngram=ng, temperature=1.0 if t is None else float(t),
+                                   top_k=0 if k is None else max(0, int(k)), top_p=1.0 if p is None else min(1.0, float(p)))
+                self.noise = torch.empty((self.B, d.vocab), dtype=torch.float32, device=dev)
             else:
                 self.use_graphs = False
         self.cache = None
@@ -159,8 +178,19 @@ class GreedyDecoder:
         self.cache["t"] = t
         logits = eng.decode_step(self.cur, self.cache)
         r = self.timestamp_rules
-        if self.soft is not None and self.history is None and mode != 0:
+        if self.soft is not None and self.history is None and self.sample is None and mode != 0:
             self._select_soft(logits, t + 1, mode, no_eos)
+            return
+        if self.sample is not None and mode != 0:
+            # (`noise` holds this position's draw: `_run_step` filled it just before this launch / this graph's replay)
+            eng.ops.sample_select(
+                logits, d.vocab, self.tokens, t + 1, self.cur, self.noise, suppress=self.suppress,
+                begin_suppress=self.begin_suppress, first=(mode == 1), no_eos=no_eos,
+                ts_begin=-1 if r is None else r["no_timestamps_token_id"] + 1,
+                max_initial=-1 if (r is None or r.get("max_initial_timestamp_index") is None)
+                else r["max_initial_timestamp_index"],
+                begin_index=1 if r is None else r["begin_index"], eos=-1 if self.eos is None else self.eos,
+                fill=self.fill, done=self.done, **self.sample)
             return
         # logits processors of the reference (min-new-tokens, begin-suppress, suppress, timestamp rules), argmax and the
         # EOS bookkeeping in one launch (csrc/decode.hip); the next token lands in tokens[:, t+1] and in cur
@@ -208,6 +238,8 @@ class GreedyDecoder:
         self.cur.copy_(nxt.view(B, 1))
 
     def _run_step(self, t, mode, no_eos=False):
+        if self.sample is not None and mode != 0:
+            self.noise.exponential_(1.0, generator=self.soft.get("generator"))
         if not self.use_graphs:
             self._step(t, mode, no_eos)
             return

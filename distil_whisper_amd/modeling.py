@@ -781,8 +781,11 @@ class WhisperForConditionalGeneration(nn.Module):
         Greedy decoding also takes GenerationMixin's `repetition_penalty` and `no_repeat_ngram_size`, in one window and in the
         seek loop: the selection kernel applies them (dw_greedy_select_history), so `use_graphs=True` holds with them.
         Single-window decoding takes plain sampling as well (a positive `temperature`, as in the reference's
-        generate_with_fallback, with `top_k` / `top_p`): decoding.GreedyDecoder `soft`, eager torch ops -- token for token the
-        reference's on the same device and seed.
+        generate_with_fallback, with `top_k` / `top_p`): decoding.GreedyDecoder `soft`.  The selection kernel samples as well
+        (dw_sample_select: processors, warpers and the draw in one launch on Exponential(1) noise that torch's generator draws,
+        which is what `torch.multinomial` does for one draw per row), so `use_graphs=True` holds; DW_SAMPLE_TORCH=1 keeps the
+        eager torch ops.  The tokens are those of the torch ops on the same device and seed, except where the top-p boundary
+        cuts through a group of equal scores (the kernel keeps the group whole, the reference's sort splits it).
         Arguments this path does not implement RAISE (nothing is silently ignored): group beam search, those three options
         combined with beams / an assistant / `use_cache=False`, plain sampling inside the seek loop, the two history options with
         `condition_on_prev_tokens=True` over several utterances, the fallback heuristics outside the seek loop, custom logits
@@ -1094,7 +1097,8 @@ class WhisperForConditionalGeneration(nn.Module):
             independent, so here rows are decoded in groups of equal prompt length (no pads, same positions);
           * fallback (TF:970-1116, 1243-1287): a window whose zlib compression ratio of the token bytes exceeds
             `compression_ratio_threshold` or whose average log-probability is below `logprob_threshold` is decoded
-            again at the next temperature (sampling; the random stream is this process's, not the reference's);
+            again at the next temperature (sampling; the random stream is this process's, not the reference's; each step is one
+            noise draw and one dw_sample_select launch where the ops have it);
             `no_speech_threshold`: P(<|nospeech|>) after <|startoftranscript|> above it together with a low average
             log-probability skips the window.  The scores are recomputed by one teacher-forced decoder pass.
           * prompt_ids (`processor.get_prompt_ids`, run_eval.py:709-710; prompt_condition_type "first-segment"): without
@@ -1116,13 +1120,15 @@ class WhisperForConditionalGeneration(nn.Module):
           * repetition_penalty / no_repeat_ngram_size (the reference hands its generation config to GenerationMixin.generate for
             every window, TF `generate_with_fallback`): the greedy pass of a window runs them inside the selection kernel
             (decoding.GreedyDecoder `soft`), over the window's decoder prompt and tokens -- previous-text prompt included;
-            sampled fallback passes and the threshold scores see them through `processed`.  Not with beams or an assistant,
+            sampled fallback passes apply them in the sampling kernel (or through `processed` on the torch path) and the
+            threshold scores see them through `processed`.  Not with beams or an assistant,
             and not with condition_on_prev_tokens over several utterances (see the message below).
         -> per utterance the list of segments {"start", "end", "tokens"}."""
         import math
         import zlib
         from . import generation as G
-        from .decoding import GreedyDecoder, apply_no_repeat_ngram, apply_repetition_penalty, apply_timestamp_rules
+        from .decoding import (SAMPLE_TORCH_ENV, GreedyDecoder, apply_no_repeat_ngram, apply_repetition_penalty,
+                               apply_timestamp_rules)
         eng, d = self.engine, self.dims
         B = input_features.shape[0]
         rep_pen = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
@@ -1194,6 +1200,10 @@ class WhisperForConditionalGeneration(nn.Module):
             sc = sc.masked_fill(sup[None, :], float("-inf"))
             return apply_timestamp_rules(sc, hist, n, P, nts, eos, max_initial_timestamp_index)
 
+        # the sampled passes select inside the kernel (dw_sample_select) where the ops have it: per step one `exponential_` draw
+        # of the shape [r, V] that `torch.multinomial` would draw itself, plus one launch; DW_SAMPLE_TORCH=1 keeps the torch ops
+        sample_kernel = hasattr(eng.ops, "sample_select") and os.environ.get(SAMPLE_TORCH_ENV, "0") in ("", "0")
+
         def sample(enc, ids, max_new, min_new, temp):
             """Multinomial sampling at temperature `temp` over the processed scores (fallback passes)."""
             r, P = ids.shape
@@ -1201,18 +1211,33 @@ class WhisperForConditionalGeneration(nn.Module):
             toks = torch.full((r, P + max_new), pad, dtype=torch.long, device=dev)
             toks[:, :P] = ids
             done = torch.zeros(r, dtype=torch.bool, device=dev)
-            logits = eng.decode_multi(ids, cache).view(r, P, -1)[:, -1, :V]
+            logits = eng.decode_multi(ids, cache).view(r, P, -1)[:, -1]
+            if sample_kernel:
+                noise = torch.empty((r, V), dtype=torch.float32, device=dev)
+                cur = torch.empty((r, 1), dtype=torch.long, device=dev)
             n = P
             while True:
-                pr = torch.softmax(processed(logits.float(), toks, n, P, min_new) / temp, -1)
-                nxt = torch.multinomial(pr, 1)[:, 0]
-                nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
-                toks[:, n] = nxt
-                done = done | (nxt == eos)
+                if sample_kernel:
+                    # processors, temperature, the draw and the EOS / pad bookkeeping in one launch (stepping stays eager: r
+                    # changes from pass to pass); the generator is consumed as by the multinomial below
+                    noise.exponential_(1.0)
+                    eng.ops.sample_select(
+                        logits, V, toks, n, cur, noise, suppress=sup.view(torch.uint8), begin_suppress=bsup.view(torch.uint8),
+                        first=(n == P), no_eos=(n - P < min_new), ts_begin=tb,
+                        max_initial=-1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index),
+                        begin_index=P, eos=eos, fill=pad, done=done, repetition_penalty=1.0 if rep_pen is None else rep_pen,
+                        no_repeat_ngram=ngram, temperature=temp)
+                    nxt = cur[:, 0]
+                else:
+                    pr = torch.softmax(processed(logits[:, :V].float(), toks, n, P, min_new) / temp, -1)
+                    nxt = torch.multinomial(pr, 1)[:, 0]
+                    nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
+                    toks[:, n] = nxt
+                    done = done | (nxt == eos)
                 n += 1
                 if n >= P + max_new or bool(done.all()):
                     break
-                logits = eng.decode_step(nxt[:, None].contiguous(), cache)[:, :V]
+                logits = eng.decode_step(nxt[:, None].contiguous(), cache)
             return toks[:, :n]
 
         def scores_of(enc, ids, gens, min_new):

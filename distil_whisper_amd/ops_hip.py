@@ -102,6 +102,9 @@ _SIGS = {
     "dw_greedy_select_history": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                                  [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_float, C.c_int, C.c_void_p], C.c_int),
+    "dw_sample_select": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
+                         [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                          C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "dw_cross_attn_probs": ([C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int64,
                                                                                                     C.c_float, C.c_void_p], C.c_int),
     "dw_align_prepare": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -654,6 +657,25 @@ class HipOps:
             int(begin_index), int(eos), int(fill), _p(done), _p(cur), float(repetition_penalty), int(no_repeat_ngram),
             self._stream()), "greedy_select_history")
 
+    def sample_select(self, logits, V, tokens, n, cur, noise, *, suppress=None, begin_suppress=None, first=False, no_eos=False,
+                      ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, fill=-1, done=None, repetition_penalty=1.0,
+                      no_repeat_ngram=0, temperature=1.0, top_k=0, top_p=1.0):
+        """The sampled step in one launch: the processed scores of `greedy_select_history`, then temperature / top-k / top-p and
+        the draw argmax softmax(s) / noise.  noise f32 [B, >= V]: `noise.exponential_(1.0, generator=g)` makes the token the one
+        `torch.multinomial(softmax(s), 1, generator=g)` draws."""
+        B = tokens.shape[0]
+        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous()
+        assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= B
+        assert noise.dtype == torch.float32 and noise.stride(1) == 1 and noise.shape[0] >= B and noise.shape[1] >= V
+        for m in (suppress, begin_suppress):
+            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
+        assert done is None or (done.dtype == torch.bool and done.is_contiguous())
+        self._chk(self.lib.dw_sample_select(
+            _p(logits), B, int(V), logits.stride(0), _p(suppress), _p(begin_suppress), int(first), int(no_eos), int(ts_begin),
+            int(max_initial), _p(tokens), tokens.stride(0), int(n), int(begin_index), int(eos), int(fill), _p(done), _p(cur),
+            float(repetition_penalty), int(no_repeat_ngram), float(temperature), int(top_k), float(top_p), _p(noise),
+            noise.stride(0), self._stream()), "sample_select")
+
     # ---- token-level timestamps (csrc/align.hip; TF:generation_whisper.py:241-381) ------------------------------------
     def cross_attn_probs(self, q, k, heads, probs, slot0, B, L, Lk, kv_batch_rows=None, scale=0.125):
         """probs[:, slot0:slot0 + len(heads), :, :Lk] = softmax(scale * q k^T) of the listed heads (int32, on the device).
@@ -802,6 +824,7 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("sumsq", "sumsq"), ("embed_fwd", "embed"), ("embed_bwd", "embed"), ("im2col_mel", "conv_aux"),
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),
                     ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("greedy_select_history", "select"),
+                    ("sample_select", "select"),
                     ("cross_attn_probs", "align"),
                     ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score"), ("dropout_fwd", "dropout_fwd"),
                     ("dropout_bwd", "dropout_bwd")):

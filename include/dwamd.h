@@ -288,6 +288,23 @@ int dw_greedy_select_history(const void* logits, int B, int V, int64_t ld, const
                              const uint8_t* begin_suppress, int first, int no_eos, int forced, int ts_begin, int max_initial,
                              int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, int fill, uint8_t* done,
                              int64_t* cur, float repetition_penalty, int no_repeat_ngram, void* stream);
+/* The sampled step (`generate(do_sample=True, temperature=, top_k=, top_p=)`: TF:generation/utils.py `_get_logits_processor` +
+ * `_sample`; the fallback passes of TF:generation_whisper.py `generate_with_fallback`, run_eval.py:690-739) in one launch.  The
+ * processed score of every column is the one dw_greedy_select_history judges (excluded = -inf); then, in the reference's order,
+ * TemperatureLogitsWarper (s / temperature), TopKLogitsWarper (top_k <= 0: off; else columns below the min(top_k, V)-th largest of
+ * all V scores are removed, ties at the threshold stay), TopPLogitsWarper (top_p >= 1: off; else a column is removed iff the
+ * softmax probability of all columns with a score <= its own is <= 1 - top_p; the largest always stays.  The reference removes a
+ * prefix of an ascending sort and so splits the group of equal scores at the boundary in an order that depends on the device's
+ * sort; this entry keeps that group whole), and the draw: argmax over the surviving columns of softmax(s)[c] / noise[b][c], equal
+ * quotients to the smaller column.  noise f32 [B][noise_ld]: Exponential(1) variates -- with `noise.exponential_(1, generator)`
+ * on a contiguous [B, V] tensor the token is the one torch.multinomial(softmax(s), 1, generator) draws.  A position inside the
+ * forced prefix is not sampled (there is no `forced`).  temperature finite and > 0, top_k >= 0, 0 < top_p <= 1, V <= 65536;
+ * equal inputs give equal tokens (no floating-point atomics). */
+int dw_sample_select(const void* logits, int B, int V, int64_t ld, const uint8_t* suppress,
+                     const uint8_t* begin_suppress, int first, int no_eos, int ts_begin, int max_initial,
+                     int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, int fill, uint8_t* done,
+                     int64_t* cur, float repetition_penalty, int no_repeat_ngram, float temperature, int top_k,
+                     float top_p, const float* noise, int64_t noise_ld, void* stream);
 
 /* ---- a11: one decoder pass of cached greedy decoding as ONE call (the `decode_step` entry of SURVEY.md 8b).
  * Replaces `WhisperDecoder.forward` + `proj_out` on the cache branch (TF:modeling_whisper.py:690-795, 312-335, 1080)
