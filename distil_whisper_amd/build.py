@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdwamd.so")
 SOURCES = ["gemm.hip", "gemm_tile256.hip", "gemm_tile128.hip", "gemm_wp8_nn.hip", "gemm_wp8_nt.hip", "gemm_wp8_m320.hip", "gemm_wp8_m128.hip",
-           "gemm_wp16_nn.hip", "gemm_wp16_tt.hip", "gemm_wp16_small.hip", "gemm_skinny.hip", "attention.hip", "norm.hip", "loss.hip", "logmel.hip", "elementwise.hip", "optim.hip", "decode.hip", "align.hip", "score.hip", "dropout.hip"]
+           "gemm_wp16_nn.hip", "gemm_wp16_tt.hip", "gemm_wp16_small.hip", "gemm_skinny.hip", "attention.hip", "norm.hip", "loss.hip", "logmel.hip", "elementwise.hip", "optim.hip", "decode.hip", "beam.hip", "align.hip", "score.hip", "dropout.hip"]
 # -munsafe-fp-atomics: float atomicAdd becomes the hardware global_atomic_add_f32 instead of a CAS loop
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-munsafe-fp-atomics"]
 
@@ -41,7 +41,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_kernel.h"), os.path.join(CSRC, "gemm_wp.h"), os.path.join(CSRC, "gemm_wp16.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_kernel.h"), os.path.join(CSRC, "gemm_wp.h"), os.path.join(CSRC, "gemm_wp16.h"), os.path.join(CSRC, "select_rules.h"),
                os.path.join(HERE, "..", "include", "dwamd.h")]
     objs, procs = [], []
     flags = FLAGS + (["-DDW_ABLATE"] if os.environ.get("DW_ABLATE") else [])   # timing-experiment kernels (tools/attn_ablate.py)

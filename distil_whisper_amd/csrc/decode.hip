@@ -17,6 +17,7 @@
 // TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper (TF:logits_process.py, in TF:utils.py `_get_logits_processor`'s
 // order), `softmax` + `torch.multinomial` of TF:utils.py `_sample`, as reached from run_eval.py:690-739 (temperature fallback).
 #include "common.h"
+#include "select_rules.h"                           // SEL_NT, Best / block_best, row_rules, rule_masks_of
 #include "../../include/dwamd.h"
 
 // dw_debug_set key 7 (A/B): bit 0 LayerNorm-on-load off, bit 1 K/V append fusion off, bit 2 / bit 3: the self- / cross-attention of
@@ -26,27 +27,7 @@
 // through L2 (157 MB against the GEMV's 9.8 MB from HBM) for a 5 us attention.
 int g_decode_fuse_off = 4;
 
-#define SEL_NT 1024
 #define NEG_BIG_D (-1.0e30f)
-
-struct Best { float v; int i; };
-__device__ __forceinline__ Best better(Best a, Best b) {      // larger value wins, ties go to the smaller index
-    return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
-__device__ __forceinline__ Best block_best(Best x, Best* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        Best y; y.v = __shfl_xor(x.v, o); y.i = __shfl_xor(x.i, o);
-        x = better(x, y);
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) red[wave] = x;
-    __syncthreads();
-    Best t = red[0];
-    for (int i = 1; i < SEL_NT / 64; ++i) t = better(t, red[i]);
-    return t;
-}
 
 // HIST (dw_greedy_select_history): the two history-dependent default processors of GenerationMixin, which the reference runs in
 // front of Whisper's own (TF `_get_logits_processor`): RepetitionPenaltyLogitsProcessor -- a column whose id occurs in
@@ -89,46 +70,10 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
         __syncthreads();
     }
     auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
-    const bool ts_mode = tb >= 0;
-    const int tsb = ts_mode ? tb : V + 1;          // first timestamp id (beyond the vocabulary when the rules are off)
-    // ---- row state of the timestamp rules (WhisperTimeStampLogitsProcessor) ----
-    bool last_ts = false, pen_ts = true, any_ts = false;
-    int ts_last = 0;
-    const int L = n - begin_index;
-    if (ts_mode && L >= 1) {
-        last_ts = row_tok[n - 1] >= tsb;
-        pen_ts = L >= 2 ? row_tok[n - 2] >= tsb : true;
-        int pos = 0;                               // 1-based position (within the generated part) of the last timestamp
-        for (int i = tid; i < L; i += SEL_NT) pos = row_tok[begin_index + i] >= tsb ? max(pos, i + 1) : pos;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pos = max(pos, __shfl_xor(pos, o));
-        if ((tid & 63) == 0) redi[tid >> 6] = pos;
-        __syncthreads();
-        pos = 0;
-        for (int i = 0; i < SEL_NT / 64; ++i) pos = max(pos, redi[i]);
-        any_ts = pos > 0;
-        if (any_ts) {
-            const int last_val = (int)row_tok[begin_index + pos - 1];
-            ts_last = (last_ts && !pen_ts) ? last_val : last_val + 1;
-        }
-    }
-    // Every rule is a predicate on the column alone once the row state is known: two allowed id intervals (text /
-    // special ids below the first timestamp, timestamp ids), two single banned ids, and the byte masks.
-    int tlo = 0, thi = ts_mode ? tsb : V, slo = V, shi = V;       // allowed: [tlo, thi) and [slo, shi)
-    const int ban_eos = no_eos ? eos : -1, ban_nots = ts_mode ? tsb - 1 : -1;
-    if (ts_mode) {
-        if (L >= 1) {
-            if (last_ts && pen_ts) { slo = shi = V; }                           // after a closed pair: text only
-            else {
-                slo = any_ts ? max(tsb, ts_last) : tsb;                          // timestamps never decrease
-                if (last_ts) tlo = eos;                                         // after text + timestamp: timestamp / EOS
-            }
-        } else {
-            tlo = thi = 0;                                                      // the first sampled token is a timestamp
-            slo = tsb;
-            shi = max_initial >= 0 ? min(V, tsb + max_initial + 1) : V;
-        }
-    }
+    // row state of the timestamp rules and the allowed id intervals (select_rules.h)
+    const RowRules rr = row_rules(row_tok, n, begin_index, tb, max_initial, V, eos, no_eos, redi);
+    const bool ts_mode = rr.ts_mode;
+    const int tsb = rr.tsb, tlo = rr.tlo, thi = rr.thi, slo = rr.slo, shi = rr.shi, ban_eos = rr.ban_eos, ban_nots = rr.ban_nots;
     auto allowed = [&](int c) -> bool {               // (used by the probability-mass pass below)
         if (suppress && suppress[c]) return false;
         if (first && begin_suppress && begin_suppress[c]) return false;
@@ -139,19 +84,7 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     // (the byte masks are fetched four columns at a time; the next chunk is requested before the current one is judged)
     const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
     Best bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
-    auto masks_of = [&](int c0) -> unsigned {          // byte e != 0: column c0 + e is suppressed
-        unsigned mask = 0;
-        if (word_masks && c0 + 3 < V) {                 // (uniform except in the last chunk of a row)
-            if (suppress) mask |= *(const unsigned*)(suppress + c0);
-            if (first && begin_suppress) mask |= *(const unsigned*)(begin_suppress + c0);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (c0 + e < V && ((suppress && suppress[c0 + e]) || (first && begin_suppress && begin_suppress[c0 + e])))
-                    mask |= 0xffu << (8 * e);
-        }
-        return mask;
-    };
+    auto masks_of = [&](int c0) -> unsigned { return rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V); };
     // A row lives on ONE CU (one workgroup), so the kernel is bound by instructions per column, not by bytes: a chunk of
     // four columns that lies inside one allowed interval with no mask bit and no banned id (almost every chunk) takes
     // the short path -- a compare and two selects per column; ascending order within a thread makes the strict compare
@@ -410,58 +343,13 @@ __global__ __launch_bounds__(SEL_NT) void sample_select_kernel(
     }
     __syncthreads();
     auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
-    const bool ts_mode = tb >= 0;
-    const int tsb = ts_mode ? tb : V + 1;
-    bool last_ts = false, pen_ts = true, any_ts = false;
-    int ts_last = 0;
-    const int L = n - begin_index;
-    if (ts_mode && L >= 1) {
-        last_ts = row_tok[n - 1] >= tsb;
-        pen_ts = L >= 2 ? row_tok[n - 2] >= tsb : true;
-        int pos = 0;
-        for (int i = tid; i < L; i += SEL_NT) pos = row_tok[begin_index + i] >= tsb ? max(pos, i + 1) : pos;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pos = max(pos, __shfl_xor(pos, o));
-        if ((tid & 63) == 0) redi[tid >> 6] = pos;
-        __syncthreads();
-        pos = 0;
-        for (int i = 0; i < SEL_NT / 64; ++i) pos = max(pos, redi[i]);
-        any_ts = pos > 0;
-        if (any_ts) {
-            const int last_val = (int)row_tok[begin_index + pos - 1];
-            ts_last = (last_ts && !pen_ts) ? last_val : last_val + 1;
-        }
-    }
-    int tlo = 0, thi = ts_mode ? tsb : V, slo = V, shi = V;
-    const int ban_eos = no_eos ? eos : -1, ban_nots = ts_mode ? tsb - 1 : -1;
-    if (ts_mode) {
-        if (L >= 1) {
-            if (last_ts && pen_ts) { slo = shi = V; }
-            else {
-                slo = any_ts ? max(tsb, ts_last) : tsb;
-                if (last_ts) tlo = eos;
-            }
-        } else {
-            tlo = thi = 0;
-            slo = tsb;
-            shi = max_initial >= 0 ? min(V, tsb + max_initial + 1) : V;
-        }
-    }
+    // row state of the timestamp rules and the allowed id intervals (select_rules.h)
+    const RowRules rr = row_rules(row_tok, n, begin_index, tb, max_initial, V, eos, no_eos, redi);
+    const bool ts_mode = rr.ts_mode;
+    const int tsb = rr.tsb, tlo = rr.tlo, thi = rr.thi, slo = rr.slo, shi = rr.shi, ban_eos = rr.ban_eos, ban_nots = rr.ban_nots;
     // ---- 1. processed scores into registers: slot 4 i + e holds column tid * 4 + i * 4096 + e (-inf: excluded or beyond V) ----
     const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
-    auto masks_of = [&](int c0) -> unsigned {
-        unsigned mask = 0;
-        if (word_masks && c0 + 3 < V) {
-            if (suppress) mask |= *(const unsigned*)(suppress + c0);
-            if (first && begin_suppress) mask |= *(const unsigned*)(begin_suppress + c0);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (c0 + e < V && ((suppress && suppress[c0 + e]) || (first && begin_suppress && begin_suppress[c0 + e])))
-                    mask |= 0xffu << (8 * e);
-        }
-        return mask;
-    };
+    auto masks_of = [&](int c0) -> unsigned { return rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V); };
     float s[NCH * 4];
     float btv = -INFINITY, bsv = -INFINITY;            // best allowed text / timestamp score (mass rule)
     {

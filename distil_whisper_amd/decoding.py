@@ -401,19 +401,117 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
     return ids, drafted, accepted
 
 
+# DW_BEAM_TORCH=1 (read when a beam search starts): the step stays on the torch ops of `beam_step_torch` on every engine, as on ops
+# without `beam_candidates` / `beam_update` -- the A/B leg of tools/bench_beam.py and the reference leg of tests/test_beam_step_gpu.py
+BEAM_TORCH_ENV = "DW_BEAM_TORCH"
+BEAM_NEG = -1.0e9
+
+
+def _gather_beams(t, idx):                               # t [B, n, ...], idx [B, m] -> [B, m, ...]
+    ix = idx
+    while ix.dim() < t.dim():
+        ix = ix.unsqueeze(-1)
+    return torch.gather(t, 1, ix.expand(*idx.shape, *t.shape[2:]))
+
+
+def _top_stable(x, k):
+    """Indices of the k largest per row, equal values in ascending index order (torch.topk leaves that order unspecified; the
+    kernels of csrc/beam.hip break ties the same way).  x [B, m] with m a few dozen."""
+    return torch.sort(x, dim=1, descending=True, stable=True)[1][:, :k]
+
+
+def beam_step_torch(st, logits, cur, cfg):
+    """One step of `beam_search_decode` as torch ops (the path of oracle.ref_ops, of CPU runs and of DW_BEAM_TORCH=1): from the
+    logits [B * k, V] of position `cur` to the new state.  st: dict(running, sequences int64 [B, k, max_length]; run_scores,
+    beam_scores f32 [B, k]; finished bool [B, k]; lengths int64 [B, k]; unsat bool [B, 1]), replaced in place.  cfg:
+    dict(P, max_length, nb, V, eos, min_new_tokens, length_penalty, early_stopping, sup, bsup -- bool [V] masks or None --,
+    timestamp_rules).  Returns (src_rows int64 [B * k]: the row each new beam continues, go_on: 0-dim bool tensor).
+    Among equal scores the lower index wins wherever the order can matter (the two small top-k)."""
+    P, max_length, nb, V, eos = cfg["P"], cfg["max_length"], cfg["nb"], cfg["V"], cfg["eos"]
+    length_penalty, early_stopping, tr = cfg["length_penalty"], cfg["early_stopping"], cfg["timestamp_rules"]
+    running, sequences, run_scores = st["running"], st["sequences"], st["run_scores"]
+    beam_scores, finished, lengths, unsat = st["beam_scores"], st["finished"], st["lengths"], st["unsat"]
+    B = running.shape[0]
+    dev = running.device
+    keep = 2 * nb                                       # (number of EOS ids + 1) * num_beams continuations per utterance
+    neg = BEAM_NEG
+    lp = torch.log_softmax(logits.float(), dim=-1)
+    flat = running[:, :, :cur].reshape(B * nb, cur)
+    if cur - P < int(cfg["min_new_tokens"]):
+        lp[:, eos] = float("-inf")
+    if cur == P and cfg["bsup"] is not None:
+        lp = lp.masked_fill(cfg["bsup"][None, :], float("-inf"))
+    if cfg["sup"] is not None:
+        lp = lp.masked_fill(cfg["sup"][None, :], float("-inf"))
+    if tr is not None:
+        lp = apply_timestamp_rules(lp, flat, cur, tr["begin_index"], tr["no_timestamps_token_id"], eos,
+                                   tr.get("max_initial_timestamp_index"))
+    acc = (lp.view(B, nb, V) + run_scores[:, :, None]).reshape(B, nb * V)
+    # equal scores go to the lower flat index beam * V + token, as in the kernels: torch.topk leaves their order unspecified, and
+    # bf16 logits give one beam's best columns equal scores all the time.  (Twice as many as needed are taken and put in order, so
+    # the rule holds unless more than `keep` columns tie with the last one kept.)
+    top_lp, top_ix = torch.topk(acc, k=min(2 * keep, acc.shape[1]))
+    by_ix = torch.sort(top_ix, dim=1, stable=True)[1]
+    top_lp, top_ix = torch.gather(top_lp, 1, by_ix), torch.gather(top_ix, 1, by_ix)
+    by_lp = _top_stable(top_lp, keep)
+    top_lp, top_ix = torch.gather(top_lp, 1, by_lp), torch.gather(top_ix, 1, by_lp)
+    src_beam, tok = top_ix // V, top_ix % V
+    top_seq = _gather_beams(running, src_beam)
+    top_seq[:, :, cur] = tok
+    hits = (tok == eos) | (cur + 1 >= max_length)
+    # open beams carried to the next step
+    open_lp = top_lp + hits.float() * neg
+    nxt = _top_stable(open_lp, nb)
+    st["running"] = _gather_beams(top_seq, nxt)
+    st["run_scores"] = run_scores = _gather_beams(open_lp, nxt)
+    src_rows = (_gather_beams(src_beam, nxt) + torch.arange(B, device=dev)[:, None] * nb).reshape(-1)
+    # finished hypotheses: only the best num_beams continuations may finish
+    top_mask = torch.arange(keep, device=dev) < nb
+    just = hits & top_mask[None, :]
+    fin_lp = top_lp / float((cur + 1 - P) ** length_penalty)
+    fin_lp = fin_lp + (finished.all(-1, keepdim=True) & (early_stopping is True)).float() * neg
+    fin_lp = fin_lp + (~unsat).float() * neg
+    fin_lp = fin_lp + (~just).float() * neg
+    m_seq = torch.cat([sequences, top_seq], 1)
+    m_sc = torch.cat([beam_scores, fin_lp], 1)
+    m_fin = torch.cat([finished, just], 1)
+    m_len = torch.cat([lengths, torch.full((B, keep), cur + 1 - P, dtype=lengths.dtype, device=dev)], 1)
+    best = _top_stable(m_sc, nb)
+    st["sequences"], st["beam_scores"] = _gather_beams(m_seq, best), _gather_beams(m_sc, best)
+    st["finished"], st["lengths"] = _gather_beams(m_fin, best), _gather_beams(m_len, best)
+    beam_scores, finished = st["beam_scores"], st["finished"]
+    # early-stopping heuristic and loop condition (TF `_check_early_stop_heuristic`, `_beam_search_has_unfinished_sequences`)
+    hyp_len = (max_length - P) if (early_stopping == "never" and length_penalty > 0.0) else (cur + 1 - P)
+    best_running = run_scores[:, :1] / float(hyp_len ** length_penalty)
+    worst_fin = torch.where(finished, beam_scores.min(1, keepdim=True)[0], torch.full_like(beam_scores, neg))
+    st["unsat"] = unsat = unsat & (best_running > worst_fin).any(-1, keepdim=True)
+    go_on = unsat.any() & ~hits.all()
+    if early_stopping is True:
+        go_on = go_on & ~finished.all()
+    return src_rows, go_on
+
+
 def beam_search_decode(engine, enc_out, prompt_ids, max_new_tokens, num_beams, eos_token_id, pad_token_id=None,
                        suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=0, length_penalty=1.0,
-                       early_stopping=False, timestamp_rules=None):
+                       early_stopping=False, timestamp_rules=None, return_scores=False, check_every=4):
     """Beam search over the KV-cache decoder: `generate(num_beams=k)` of the reference (run_eval.py:143, 693;
     run_distillation.py:1428-1436; TF:generation/utils.py `_beam_search`, the vectorised v5 algorithm) -- per step the
     log-softmax of every live beam plus its running score, the top 2k continuations per utterance, the k best open ones
     carried on (their K/V cache rows gathered in place), finished ones merged into the k best finished hypotheses
     under the length penalty, and the early-stopping heuristic of `early_stopping` in {False, True, "never"}.
     The decoder passes are the engine's cached passes over B * k rows (prompt prefill in one multi-token pass, then
-    token steps); the bookkeeping is index arithmetic on [B, 2k] tensors on the device.
-    prompt_ids int64 [B, P] -> sequences int64 [B, P + n] (best finished hypothesis per row, padded with pad_token_id)."""
+    token steps).  Where the engine's ops have `beam_candidates` / `beam_update` (csrc/beam.hip) the step is two entry calls on
+    device-resident state: the loop condition lands in a device word that the host reads every `check_every` steps (once it is
+    set the kernels leave the state alone), so nothing synchronises in between.  On other ops (oracle.ref_ops, CPU), with
+    DW_BEAM_TORCH=1, or for num_beams > 16 / a vocabulary > 65 536 the step is `beam_step_torch`, which reads the loop condition
+    every step.  Equal scores: the lower flat index beam * V + token wins in the kernels (torch.topk's order is unspecified).
+    prompt_ids int64 [B, P] -> sequences int64 [B, P + n] (best finished hypothesis per row, padded with pad_token_id).
+    return_scores=True -> (sequences, sequences_scores f32 [B], prefill_logits [B, P, V]): the best hypothesis' length-penalised
+    score (`beam_scores[:, 0]`, what TF `_beam_search` returns as `sequences_scores`) and the logits of the prompt prefill of
+    each utterance's beam 0 at every prompt position (the seek loop reads its no-speech probability there)."""
     dev = prompt_ids.device
     d = engine.dims
+    ops = engine.ops
     B, P = prompt_ids.shape
     nb, V = int(num_beams), d.vocab
     max_length = P + int(max_new_tokens)
@@ -421,87 +519,91 @@ def beam_search_decode(engine, enc_out, prompt_ids, max_new_tokens, num_beams, e
         raise ValueError("beam search needs eos_token_id")
     eos = int(eos_token_id)
     fill = int(pad_token_id) if pad_token_id is not None else eos
-    keep = 2 * nb                                       # (number of EOS ids + 1) * num_beams continuations per utterance
-    neg = -1.0e9
+    keep = 2 * nb
+    neg = BEAM_NEG
+    use_kernels = (hasattr(ops, "beam_candidates") and hasattr(ops, "beam_update") and ops.beam_supported(nb, V)
+                   and os.environ.get(BEAM_TORCH_ENV, "0") in ("", "0"))
 
-    def mask_of(ids):
-        m = torch.zeros(V, dtype=torch.bool, device=dev)
-        if ids:
-            m[torch.as_tensor(list(ids), dtype=torch.long, device=dev)] = True
+    def mask_of(ids, dtype):                             # decided once, on the host: no per-step `.any()` round trip
+        ids = [int(t) for t in (ids or []) if 0 <= int(t) < V]
+        if not ids:
+            return None
+        m = torch.zeros(V, dtype=dtype, device=dev)
+        m[torch.as_tensor(ids, dtype=torch.long, device=dev)] = 1
         return m
-    sup, bsup = mask_of(suppress_tokens), mask_of(begin_suppress_tokens)
-
-    def gather(t, idx):                                  # t [B, n, ...], idx [B, m] -> [B, m, ...]
-        ix = idx
-        while ix.dim() < t.dim():
-            ix = ix.unsqueeze(-1)
-        return torch.gather(t, 1, ix.expand(*idx.shape, *t.shape[2:]))
 
     Lk, D = d.max_src, d.d_model
     enc_rep = enc_out[:B * Lk].view(B, Lk, D).repeat_interleave(nb, 0).reshape(B * nb * Lk, D).contiguous()
     cache = engine.decode_init(enc_rep, B * nb, max_length)
     running = torch.full((B, nb, max_length), fill, dtype=torch.long, device=dev)
     running[:, :, :P] = prompt_ids[:, None, :]
-    sequences = running.clone()
     run_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     run_scores[:, 1:] = neg
-    beam_scores = torch.full((B, nb), neg, dtype=torch.float32, device=dev)
-    finished = torch.zeros((B, nb), dtype=torch.bool, device=dev)
-    lengths = torch.zeros((B, nb), dtype=torch.long, device=dev)          # generated tokens of the finished hypotheses
-    unsat = torch.ones((B, 1), dtype=torch.bool, device=dev)
-    top_mask = torch.cat([torch.ones(nb, dtype=torch.bool, device=dev), torch.zeros(keep - nb, dtype=torch.bool, device=dev)])
+    st = dict(running=running, sequences=running.clone(), run_scores=run_scores,
+              beam_scores=torch.full((B, nb), neg, dtype=torch.float32, device=dev),
+              finished=torch.zeros((B, nb), dtype=torch.bool, device=dev),
+              lengths=torch.zeros((B, nb), dtype=torch.int32 if use_kernels else torch.long, device=dev),   # generated tokens
+              unsat=torch.ones((B, 1), dtype=torch.bool, device=dev))
     cur = P
-    logits = engine.decode_multi(running[:, :, :P].reshape(B * nb, P), cache).view(B * nb, P, -1)[:, -1, :V]
-    while True:
-        lp = torch.log_softmax(logits.float(), dim=-1)
-        flat = running[:, :, :cur].reshape(B * nb, cur)
-        if cur - P < int(min_new_tokens):
-            lp[:, eos] = float("-inf")
-        if cur == P and bool(bsup.any()):
-            lp = lp.masked_fill(bsup[None, :], float("-inf"))
-        if bool(sup.any()):
-            lp = lp.masked_fill(sup[None, :], float("-inf"))
-        if timestamp_rules is not None:
-            lp = apply_timestamp_rules(lp, flat, cur, timestamp_rules["begin_index"],
-                                       timestamp_rules["no_timestamps_token_id"], eos,
-                                       timestamp_rules.get("max_initial_timestamp_index"))
-        acc = (lp.view(B, nb, V) + run_scores[:, :, None]).reshape(B, nb * V)
-        top_lp, top_ix = torch.topk(acc, k=keep)
-        src_beam, tok = top_ix // V, top_ix % V
-        top_seq = gather(running, src_beam)
-        top_seq[:, :, cur] = tok
-        hits = (tok == eos) | (cur + 1 >= max_length)
-        # open beams carried to the next step
-        open_lp = top_lp + hits.float() * neg
-        nxt = torch.topk(open_lp, k=nb)[1]
-        running = gather(top_seq, nxt)
-        run_scores = gather(open_lp, nxt)
-        src_rows = (gather(src_beam, nxt) + torch.arange(B, device=dev)[:, None] * nb).reshape(-1)
-        # finished hypotheses: only the best num_beams continuations may finish
-        just = hits & top_mask[None, :]
-        fin_lp = top_lp / float((cur + 1 - P) ** length_penalty)
-        fin_lp = fin_lp + (finished.all(-1, keepdim=True) & (early_stopping is True)).float() * neg
-        fin_lp = fin_lp + (~unsat).float() * neg
-        fin_lp = fin_lp + (~just).float() * neg
-        m_seq = torch.cat([sequences, top_seq], 1)
-        m_sc = torch.cat([beam_scores, fin_lp], 1)
-        m_fin = torch.cat([finished, just], 1)
-        m_len = torch.cat([lengths, torch.full((B, keep), cur + 1 - P, dtype=torch.long, device=dev)], 1)
-        best = torch.topk(m_sc, k=nb)[1]
-        sequences, beam_scores, finished, lengths = gather(m_seq, best), gather(m_sc, best), gather(m_fin, best), gather(m_len, best)
-        # the carried beams' K/V rows (positions < cur are live: the next pass appends position cur)
+    full = engine.decode_multi(running[:, :, :P].reshape(B * nb, P), cache)
+    logits = full.view(B * nb, P, -1)[:, -1]             # [B * k, ld], V valid columns
+    prefill = full.view(B, nb, P, -1)[:, 0, :, :V].clone() if return_scores else None
+
+    def reorder(src_rows, n):                            # the carried beams' K/V rows (positions < n are live)
         for kvc in cache["self"]:
             v = kvc.view(B * nb, max_length, -1)
-            v[:, :cur].copy_(v[src_rows, :cur])
-        cur += 1
-        # early-stopping heuristic and loop condition (TF `_check_early_stop_heuristic`, `_beam_search_has_unfinished_sequences`)
-        hyp_len = (max_length - P) if (early_stopping == "never" and length_penalty > 0.0) else (cur - P)
-        best_running = run_scores[:, :1] / float(hyp_len ** length_penalty)
-        worst_fin = torch.where(finished, beam_scores.min(1, keepdim=True)[0], torch.full_like(beam_scores, neg))
-        unsat = unsat & (best_running > worst_fin).any(-1, keepdim=True)
-        go_on = bool(unsat.any()) and not (bool(finished.all()) and early_stopping is True) and not bool(hits.all())
-        if not go_on:
-            break
-        logits = engine.decode_step(running[:, :, cur - 1].reshape(B * nb, 1).contiguous(), cache)[:, :V]
-    out_len = P + int(lengths[:, 0].max().item())
-    return sequences[:, 0, :out_len].contiguous()
+            v[:, :n].copy_(v[src_rows, :n])
+
+    def divisors(c):                                     # in double on the host, as the torch step computes them
+        hyp_len = (max_length - P) if (early_stopping == "never" and length_penalty > 0.0) else (c + 1 - P)
+        return float((c + 1 - P) ** length_penalty), float(hyp_len ** length_penalty)
+
+    if use_kernels:
+        sup, bsup = mask_of(suppress_tokens, torch.uint8), mask_of(begin_suppress_tokens, torch.uint8)
+        tr = timestamp_rules
+        R = B * nb
+        other = dict(running=torch.full_like(running, fill), sequences=torch.full_like(running, fill))
+        other["running"][:, :, :P] = prompt_ids[:, None, :]
+        other["sequences"][:, :, :P] = prompt_ids[:, None, :]
+        cand_val = torch.empty((R, keep), dtype=torch.float32, device=dev)
+        cand_tok = torch.empty((R, keep), dtype=torch.int32, device=dev)
+        stop = torch.zeros((1,), dtype=torch.int32, device=dev)
+        src_rows = torch.arange(R, dtype=torch.long, device=dev)
+        next_tok = torch.zeros((R, 1), dtype=torch.long, device=dev)
+        plan = torch.empty((4 * R,), dtype=torch.int32, device=dev)
+        while True:
+            ops.beam_candidates(
+                logits, V, st["running"].view(R, max_length), cur, st["run_scores"], cand_val, cand_tok, stop, suppress=sup,
+                begin_suppress=bsup, first=(cur == P), no_eos=(cur - P) < int(min_new_tokens),
+                ts_begin=-1 if tr is None else tr["no_timestamps_token_id"] + 1,
+                max_initial=-1 if (tr is None or tr.get("max_initial_timestamp_index") is None)
+                else tr["max_initial_timestamp_index"],
+                begin_index=1 if tr is None else tr["begin_index"], eos=eos)
+            fin_div, hyp_div = divisors(cur)
+            ops.beam_update(cand_val, cand_tok, B, nb, V, cur, P, max_length, eos, early_stopping, fin_div, hyp_div,
+                            st["running"], other["running"], st["sequences"], other["sequences"], st["run_scores"],
+                            st["beam_scores"], st["finished"], st["lengths"], st["unsat"], stop, src_rows, next_tok, plan)
+            for name in ("running", "sequences"):        # ping-pong: no row is read after another row has overwritten it
+                st[name], other[name] = other[name], st[name]
+            cur += 1
+            # (at cur == max_length every continuation was a hit: the kernel has set `stop`)
+            if cur >= max_length or ((cur - P) % int(check_every) == 0 and bool(stop.item())):
+                break
+            reorder(src_rows, cur - 1)
+            logits = engine.decode_step(next_tok, cache)
+    else:
+        cfg = dict(P=P, max_length=max_length, nb=nb, V=V, eos=eos, min_new_tokens=int(min_new_tokens),
+                   length_penalty=length_penalty, early_stopping=early_stopping, sup=mask_of(suppress_tokens, torch.bool),
+                   bsup=mask_of(begin_suppress_tokens, torch.bool), timestamp_rules=timestamp_rules)
+        while True:
+            src_rows, go_on = beam_step_torch(st, logits[:, :V], cur, cfg)
+            reorder(src_rows, cur)
+            cur += 1
+            if not bool(go_on):
+                break
+            logits = engine.decode_step(st["running"][:, :, cur - 1].reshape(B * nb, 1).contiguous(), cache)
+    out_len = P + int(st["lengths"][:, 0].max().item())
+    seqs = st["sequences"][:, 0, :out_len].contiguous()
+    if return_scores:
+        return seqs, st["beam_scores"][:, 0].clone(), prefill
+    return seqs

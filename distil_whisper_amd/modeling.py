@@ -774,7 +774,9 @@ class WhisperForConditionalGeneration(nn.Module):
         min-new-tokens / timestamp logits rules, `assistant_model` (speculative decoding), `encoder_outputs`.
         The token loop is decoding.GreedyDecoder (KV cache; `use_graphs` replays the per-position launch sequence from
         HIP graphs; `use_cache=False` re-decodes the whole prefix every step and exists as a cross-check).
-        `num_beams > 1` runs decoding.beam_search_decode (TF `_beam_search`).  `return_timestamps=True` (without
+        `num_beams > 1` runs decoding.beam_search_decode (TF `_beam_search`; its step is two kernel entries, dw_beam_candidates and
+        dw_beam_update, DW_BEAM_TORCH=1 keeps the torch step); in the seek loop it combines with the fallback thresholds, the beam
+        pass being judged by its hypothesis' `sequences_scores`.  `return_timestamps=True` (without
         `force_unique_generate_call`) and inputs longer than 30 s run the reference's timestamp seek loop
         (`seek_decode`, TF:784-903) with `condition_on_prev_tokens`, the fallback thresholds (`temperature` tuple,
         `compression_ratio_threshold`, `logprob_threshold`) and the `no_speech_threshold` skip.
@@ -1109,7 +1111,19 @@ class WhisperForConditionalGeneration(nn.Module):
             the place of <|startofprev|> in front of the previous tokens of every window (TF:1887-1888);
           * num_beams > 1 (run_eval.py:693 / run_pseudo_labelling.py `--generation_num_beams`): the temperature-0 pass of a
             window is a beam search (decoding.beam_search_decode with the timestamp rules); sampled fallback passes use
-            one beam like the reference (TF:1010-1012).  The score-based thresholds (logprob / no-speech) are greedy-only;
+            one beam like the reference (TF:1004-1005).  With `logprob_threshold` the beam pass is judged by its hypothesis'
+            `sequences_scores` (the length-penalised sum of log-probabilities) instead of the average token log-probability,
+            without a rescoring pass; the no-speech probability comes from the beam search's own prompt prefill
+            (`beam_no_speech` below says which row the reference reads); sampled passes are scored as without beams.
+            A DELIBERATE DEVIATION from the installed reference: `_need_fallback` (TF:1261-1273) states this rule -- `if
+            hasattr(seek_outputs[0], "sequences_scores")` -- but its per-window outputs are plain dicts, the test is false, and
+            `transformers` 5.15 instead averages, by `_retrieve_avg_logprobs`, the processed scores of EXPANDED row `index` of
+            the B * num_beams beam rows (the beam in slot `index % num_beams` of utterance `index // num_beams` at each step)
+            at the window's own tokens: a number that belongs to no hypothesis.  This package follows the stated rule, not that
+            number, so for a `logprob_threshold` between a window's `sequences_scores` and that average its fallback / skip
+            decision differs from the installed reference's.  tests/golden/beam_thresholds.json is made with the stated
+            branch reachable and records one such threshold per multilingual seed together with what the untouched reference
+            returns there (`installed_differs`); tests/test_beam_step.py pins both;
           * assistant = (engine, encode) of a draft model (run_eval.py:578-599, 706-707 with long-form inputs): the
             temperature-0 pass of a window is decoding.assisted_greedy_decode with the timestamp rules; encode(features)
             gives the assistant's encoder output of a window batch, or None when it shares this model's.
@@ -1170,9 +1184,6 @@ class WhisperForConditionalGeneration(nn.Module):
         if prev_sot is None and suppress_tokens is not None and len(suppress_tokens) >= 2:
             prev_sot = suppress_tokens[-2]
         need_scores = logprob_threshold is not None or no_speech_threshold is not None
-        if int(num_beams) > 1 and need_scores:
-            raise NotImplementedError("logprob_threshold / no_speech_threshold with beam search are not implemented on the "
-                                      "MI355X path (the reference scores beams by `sequences_scores`)")
         if no_speech_threshold is not None and logprob_threshold is None:
             raise ValueError("no_speech_threshold needs logprob_threshold (the reference compares both)")
         if token_timestamps is not None and (any(t > 0.0 for t in temps) or assistant is not None or int(num_beams) > 1):
@@ -1270,6 +1281,21 @@ class WhisperForConditionalGeneration(nn.Module):
                 nsp = torch.softmax(first, -1)[:, nts - 1]
             return avg, nsp.tolist()
 
+        def beam_no_speech(prefill, ids, P, min_new, nb):
+            """P(<|nospeech|>) of a beam-search pass as the reference's `_need_fallback` reads it.  prefill f32 / bf16 [r, P, V]: the
+            prompt-prefill logits of each utterance's beam 0.  With a decoder prompt of several start tokens
+            `WhisperNoSpeechDetection` runs the model on its own, unexpanded inputs: one row per utterance, the softmax at the
+            <|startoftranscript|> position.  With a single start token it keeps the processor scores of the first step, which in
+            beam search are the r * nb expanded rows (log-probabilities, so `exp`, not renormalised after the other processors), and
+            `_need_fallback` indexes that tensor with the UTTERANCE index (`no_speech_prob[index]`): utterance i is judged by
+            expanded row i, i.e. by utterance i // nb.  Reproduced here as it is."""
+            r = ids.shape[0]
+            if P0 > 1:
+                return torch.softmax(prefill[:, P - P0].float(), -1)[:, nts - 1].tolist()
+            lp = processed(torch.log_softmax(prefill[:, P - 1].float(), -1), ids, P, P, min_new)
+            per_row = lp[:, nts - 1].exp().tolist()
+            return [per_row[i // nb] for i in range(r)]
+
         def ratio(tokens):
             nbytes = int(math.log2(V) / 8) + 1
             raw = b"".join(int(x).to_bytes(nbytes, "little") for x in tokens)
@@ -1339,7 +1365,12 @@ class WhisperForConditionalGeneration(nn.Module):
                             begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new,
                             length_penalty=float(length_penalty), early_stopping=early_stopping,
                             timestamp_rules=dict(begin_index=P, no_timestamps_token_id=nts,
-                                                 max_initial_timestamp_index=max_initial_timestamp_index))[:, P:].tolist()
+                                                 max_initial_timestamp_index=max_initial_timestamp_index),
+                            return_scores=need_scores)
+                        if need_scores:
+                            out, beam_sc, prefill = out
+                            beam_scored = (beam_sc.tolist(), beam_no_speech(prefill, ids, P, min_new, int(num_beams)))
+                        out = out[:, P:].tolist()
                     else:
                         key = (len(pending), P, max_new, eos, pad, nts, max_initial_timestamp_index,
                                tuple(suppress_tokens or ()), tuple(begin_suppress_tokens or ()), rep_pen, ngram)
@@ -1373,7 +1404,9 @@ class WhisperForConditionalGeneration(nn.Module):
                                 seq = seq[:-npad]
                         gens.append(seq)
                     avg = nsp = None
-                    if need_scores:
+                    if need_scores and temp == 0.0 and int(num_beams) > 1 and assistant is None:
+                        avg, nsp = beam_scored           # the hypotheses' own scores: no teacher-forced pass (TF:1261-1264)
+                    elif need_scores:
                         avg, nsp = scores_of(enc, ids, gens, min_new)
                     again = []
                     for i, b in enumerate(pending):

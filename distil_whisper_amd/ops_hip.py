@@ -105,6 +105,11 @@ _SIGS = {
     "dw_sample_select": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
                          [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                           C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "dw_beam_candidates": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
+                           [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p], C.c_int),
+    "dw_beam_update": ([C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_float] * 2 + [C.c_void_p] * 4 + [C.c_int64] +
+                       [C.c_void_p] * 10, C.c_int),
     "dw_cross_attn_probs": ([C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int64,
                                                                                                     C.c_float, C.c_void_p], C.c_int),
     "dw_align_prepare": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -676,6 +681,61 @@ class HipOps:
             float(repetition_penalty), int(no_repeat_ngram), float(temperature), int(top_k), float(top_p), _p(noise),
             noise.stride(0), self._stream()), "sample_select")
 
+    # ---- beam search (csrc/beam.hip; TF:generation/utils.py `_beam_search`) ------------------------------------------------------
+    BEAM_MAX_BEAMS, BEAM_MAX_VOCAB = 16, 65536
+
+    def beam_supported(self, num_beams, V):
+        """False: dw_beam_candidates / dw_beam_update would answer DW_EUNSUP (the caller keeps its torch step)."""
+        return 1 <= int(num_beams) <= self.BEAM_MAX_BEAMS and int(V) <= self.BEAM_MAX_VOCAB
+
+    def beam_candidates(self, logits, V, tokens, n, run_scores, cand_val, cand_tok, stop, *, suppress=None, begin_suppress=None,
+                        first=False, no_eos=False, ts_begin=-1, max_initial=-1, begin_index=1, eos=0):
+        """The K = cand_val.shape[1] best continuations of every beam row: logits bf16 [R, ld], tokens int64 [R, >= n] (history
+        of the timestamp rules), run_scores f32 [R] -> cand_val f32 / cand_tok int32 [R, K]: log_softmax(logits)[c] + run_scores
+        over the columns the rules of `greedy_select` allow, value descending, then column ascending.  stop int32 [1]: non-zero
+        = nothing is written."""
+        R, K = cand_val.shape
+        assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= R
+        assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[0] >= R and tokens.shape[1] >= n
+        assert run_scores.dtype == torch.float32 and run_scores.is_contiguous() and run_scores.numel() == R
+        assert cand_val.dtype == torch.float32 and cand_val.is_contiguous()
+        assert cand_tok.dtype == torch.int32 and cand_tok.is_contiguous() and cand_tok.shape == cand_val.shape
+        assert stop.dtype == torch.int32 and stop.numel() == 1
+        for m in (suppress, begin_suppress):
+            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
+        self._chk(self.lib.dw_beam_candidates(
+            _p(logits), R, int(V), logits.stride(0), _p(suppress), _p(begin_suppress), int(first), int(no_eos), int(ts_begin),
+            int(max_initial), _p(tokens), tokens.stride(0), int(n), int(begin_index), int(eos), _p(run_scores), K, _p(cand_val),
+            _p(cand_tok), _p(stop), self._stream()), "beam_candidates")
+
+    def beam_update(self, cand_val, cand_tok, B, k, V, cur, prompt_len, max_length, eos, early_stopping, fin_div, hyp_div,
+                    running_in, running_out, sequences_in, sequences_out, run_scores, beam_scores, finished, lengths, unsat, stop,
+                    src_rows, next_tok, plan):
+        """The bookkeeping of one beam-search step for the whole batch (include/dwamd.h dw_beam_update).  running / sequences
+        int64 [B, k, L] contiguous, in and out different buffers; run_scores / beam_scores f32, finished bool, lengths int32
+        [B, k]; unsat bool [B]; stop int32 [1]; src_rows / next_tok int64 [B * k]; plan int32 [4 * B * k] scratch.
+        early_stopping: False / True / "never"."""
+        R = B * k
+        for t in (running_in, running_out, sequences_in, sequences_out):
+            assert t.dtype == torch.int64 and t.is_contiguous() and t.shape == running_in.shape and t.shape[:2] == (B, k)
+        assert cand_val.dtype == torch.float32 and cand_val.is_contiguous() and cand_val.shape == (R, 2 * k)
+        assert cand_tok.dtype == torch.int32 and cand_tok.is_contiguous() and cand_tok.shape == (R, 2 * k)
+        for t in (run_scores, beam_scores):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == R
+        assert finished.dtype == torch.bool and finished.is_contiguous() and finished.numel() == R
+        assert lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == R
+        assert unsat.dtype == torch.bool and unsat.is_contiguous() and unsat.numel() == B
+        assert stop.dtype == torch.int32 and stop.numel() == 1
+        for t in (src_rows, next_tok):
+            assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == R
+        assert plan.dtype == torch.int32 and plan.is_contiguous() and plan.numel() >= 4 * R
+        es = 2 if early_stopping == "never" else (1 if early_stopping is True else 0)
+        self._chk(self.lib.dw_beam_update(
+            _p(cand_val), _p(cand_tok), int(B), int(k), int(V), int(cur), int(prompt_len), int(max_length), int(eos), es,
+            float(fin_div), float(hyp_div), _p(running_in), _p(running_out), _p(sequences_in), _p(sequences_out),
+            running_in.shape[2], _p(run_scores), _p(beam_scores), _p(finished), _p(lengths), _p(unsat), _p(stop), _p(src_rows),
+            _p(next_tok), _p(plan), self._stream()), "beam_update")
+
     # ---- token-level timestamps (csrc/align.hip; TF:generation_whisper.py:241-381) ------------------------------------
     def cross_attn_probs(self, q, k, heads, probs, slot0, B, L, Lk, kv_batch_rows=None, scale=0.125):
         """probs[:, slot0:slot0 + len(heads), :, :Lk] = softmax(scale * q k^T) of the listed heads (int32, on the device).
@@ -824,7 +884,7 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("sumsq", "sumsq"), ("embed_fwd", "embed"), ("embed_bwd", "embed"), ("im2col_mel", "conv_aux"),
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),
                     ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("greedy_select_history", "select"),
-                    ("sample_select", "select"),
+                    ("sample_select", "select"), ("beam_candidates", "beam"), ("beam_update", "beam"),
                     ("cross_attn_probs", "align"),
                     ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score"), ("dropout_fwd", "dropout_fwd"),
                     ("dropout_bwd", "dropout_bwd")):

@@ -306,6 +306,35 @@ int dw_sample_select(const void* logits, int B, int V, int64_t ld, const uint8_t
                      int64_t* cur, float repetition_penalty, int no_repeat_ngram, float temperature, int top_k,
                      float top_p, const float* noise, int64_t noise_ld, void* stream);
 
+/* ---- beam search: one token step of `generate(num_beams=k)` (TF:generation/utils.py `_beam_search`; csrc/beam.hip).
+ * dw_beam_candidates: for each of the R = B * k beam rows, in fp32: lse = log-sum-exp over all V raw logits (the reference takes
+ * log_softmax before its processors and does not renormalise), lp[c] = logits[c] - lse where the rules of dw_greedy_select allow
+ * column c (no_eos, begin_suppress when first != 0, suppress, the timestamp rules from the row's own history tokens[r][0, n),
+ * the timestamp mass rule), -inf elsewhere; the row's K = 2k largest lp[c] + run_scores[r] go to cand_val / cand_tok [R][K],
+ * ordered by value descending, then column ascending; with fewer than K allowed columns the rest is (-inf, eos).  logits bf16
+ * [R][ld] as in dw_greedy_select; eos in [0, V).  K <= 32 and V <= 65536, else DW_EUNSUP.  stop: device word; non-zero = the
+ * search has ended, nothing is written. */
+int dw_beam_candidates(const void* logits, int R, int V, int64_t ld, const uint8_t* suppress, const uint8_t* begin_suppress,
+                       int first, int no_eos, int ts_begin, int max_initial, const int64_t* tokens, int64_t tok_ld, int n,
+                       int begin_index, int eos, const float* run_scores, int K, float* cand_val, int32_t* cand_tok,
+                       const int32_t* stop, void* stream);
+/* dw_beam_update: the bookkeeping of the step whose candidates dw_beam_candidates wrote, for the whole batch (one workgroup
+ * decides, a row-parallel launch moves the token rows).  Per utterance: the k * K candidates merged into the top K by (value
+ * descending, flat index beam * V + token ascending); hits = EOS or cur + 1 >= max_length; the k best open continuations become
+ * running_out / run_scores / src_rows (int64 [R]: the row each new beam continues, for the caller's K/V gather) / next_tok (int64
+ * [R]: the next step's input); hits among the first k are merged into sequences_out / beam_scores / finished / lengths (int32:
+ * generated tokens) with score value / fin_div; the early-stopping heuristic (early_stopping 0 = False, 1 = True, 2 = "never")
+ * with best running score / hyp_div updates unsat (uint8 [B]); the loop condition goes to *stop (1 = ended).  fin_div =
+ * (cur + 1 - prompt_len) ^ length_penalty and hyp_div = hyp_len ^ length_penalty come from the host.  Equal scores: the lower
+ * index wins.  running / sequences int64 [R][tok_ld]; in and out must be different buffers and every buffer holds the pad token
+ * beyond its hypotheses; columns [0, cur] are written.  With *stop set on entry the state is left as it is: out = in, src_rows =
+ * identity, next_tok untouched.  plan: int32 [4 * R] scratch.  k <= 16, V <= 65536, B * k <= 65535, else DW_EUNSUP. */
+int dw_beam_update(const float* cand_val, const int32_t* cand_tok, int B, int k, int V, int cur, int prompt_len, int max_length,
+                   int eos, int early_stopping, float fin_div, float hyp_div, const int64_t* running_in, int64_t* running_out,
+                   const int64_t* sequences_in, int64_t* sequences_out, int64_t tok_ld, float* run_scores, float* beam_scores,
+                   uint8_t* finished, int32_t* lengths, uint8_t* unsat, int32_t* stop, int64_t* src_rows, int64_t* next_tok,
+                   int32_t* plan, void* stream);
+
 /* ---- a11: one decoder pass of cached greedy decoding as ONE call (the `decode_step` entry of SURVEY.md 8b).
  * Replaces `WhisperDecoder.forward` + `proj_out` on the cache branch (TF:modeling_whisper.py:690-795, 312-335, 1080)
  * as reached from `generate` (run_eval.py:739, run_distillation.py:1524-1528, run_pseudo_labelling.py:861-996).
