@@ -930,8 +930,9 @@ extern "C" int dw_attn_fwd_ex(const void* q, const void* k, const void* v, void*
     if (causal == 2 && Lk < Lq) return DW_EINVAL;
     p.coff = causal == 2 ? Lk - Lq : 0;
     hipStream_t s = (hipStream_t)stream;
-    if (Lq == 1 && g_attn_decode && Lk <= 8192) {
-        // one query per (batch, head): the streaming decode kernel (the causal mask is void for a single last query)
+    if (Lq == 1 && causal != 1 && g_attn_decode && Lk <= 8192) {
+        // one query per (batch, head): the streaming decode kernel.  The mask is void for a single LAST query (causal 0 and 2);
+        // with causal == 1 the one query is query 0 and sees key 0 only: that combination takes the tile kernel below
         const size_t smem = (((size_t)Lk + 3) & ~(size_t)3) * 4 + 16 * 64 * 4 + 2 * 16 * 4;
         if (Lk >= 512 && Lk <= 16 * 8 * 12 && (g_attn_decode & 2))   // (measured slower: 111 registers -> one workgroup per CU)
             hipLaunchKernelGGL((attn_decode_kernel<16, true>), dim3(1, H, B), dim3(1024), smem, s, p);
