@@ -35,16 +35,6 @@ __global__ __launch_bounds__(SEL_NT) void beam_candidates_kernel(
     const bf16* row = logits + (long)b * ld;
     const RowRules rr = row_rules(row_tok, n, begin_index, tb, max_initial, V, eos, no_eos, redi);
     const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
-    auto block_max = [&](float x) -> float {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-        __syncthreads();
-        if ((tid & 63) == 0) redf[tid >> 6] = x;
-        __syncthreads();
-        float t = redf[0];
-        for (int i = 1; i < SEL_NT / 64; ++i) t = fmaxf(t, redf[i]);
-        return t;
-    };
     // ---- the row into registers as it is stored (bf16, slot 4 i + e holds column tid * 4 + i * 4096 + e) with one bit per slot:
     // the rules allow the column.  The fp32 scores replace it only at the end (a 1024-thread workgroup has 128 registers a lane) ----
     const int tid4 = tid * 4;
@@ -71,16 +61,16 @@ __global__ __launch_bounds__(SEL_NT) void beam_candidates_kernel(
                 const float x = bf2f(xr[i][e]);
                 inbits |= 1ull << (4 * i + e);
                 raw_max = fmaxf(raw_max, x);
-                if (!((mr[i] >> (8 * e)) & 0xffu) && rr.in_range(c)) {
+                if (column_allowed(rr, c0, e, V, mr[i])) {
                     okbits |= 1ull << (4 * i + e);
                     if (c < rr.tsb) btv = fmaxf(btv, x); else bsv = fmaxf(bsv, x);
                 }
             }
         }
     }
-    raw_max = block_max(raw_max);
-    btv = block_max(btv);
-    bsv = block_max(bsv);
+    raw_max = block_max<SEL_NT>(raw_max, redf);
+    btv = block_max<SEL_NT>(btv, redf);
+    bsv = block_max<SEL_NT>(bsv, redf);
     // ---- log-sum-exp over ALL V raw logits (the reference takes log_softmax before its processors and does not renormalise):
     // fp32 terms, summed per thread in fp32 (<= 64 terms) and across the workgroup in double ----
     auto block_sum = [&](float part) -> float {
@@ -143,10 +133,9 @@ extern "C" int dw_beam_candidates(const void* logits, int R, int V, int64_t ld, 
                                   const int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, const float* run_scores,
                                   int K, float* cand_val, int32_t* cand_tok, const int32_t* stop, void* stream) {
     DW_CLEAR_ERR();
-    if (!logits || !tokens || !run_scores || !cand_val || !cand_tok || !stop) return DW_EINVAL;
-    if (R <= 0 || V <= 0 || K < 2 || (K & 1) || n < 1 || n > tok_ld || eos < 0 || eos >= V) return DW_EINVAL;
-    if (ld < V || (ld & 3) || ((uintptr_t)logits & 7)) return DW_EINVAL;
-    if (ts_begin >= 0 && (begin_index < 1 || begin_index > n)) return DW_EINVAL;
+    if (!tokens || !run_scores || !cand_val || !cand_tok || !stop) return DW_EINVAL;
+    if (R <= 0 || K < 2 || (K & 1) || n < 1 || n > tok_ld || eos < 0 || eos >= V) return DW_EINVAL;
+    if (!select_args_ok(logits, V, ld, n, ts_begin, begin_index, eos)) return DW_EINVAL;
     if (K > 2 * BEAM_MAX_K || V > 16 * SEL_NT * 4) return DW_EUNSUP;
     auto kern = V <= 13 * SEL_NT * 4 ? beam_candidates_kernel<13> : beam_candidates_kernel<16>;
     hipLaunchKernelGGL(kern, dim3(R), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V, (long)ld, suppress,

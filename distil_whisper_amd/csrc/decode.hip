@@ -17,7 +17,7 @@
 // TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper (TF:logits_process.py, in TF:utils.py `_get_logits_processor`'s
 // order), `softmax` + `torch.multinomial` of TF:utils.py `_sample`, as reached from run_eval.py:690-739 (temperature fallback).
 #include "common.h"
-#include "select_rules.h"                           // SEL_NT, Best / block_best, row_rules, rule_masks_of
+#include "select_rules.h"                           // SEL_NT, Best / block_best and every logits rule
 #include "../../include/dwamd.h"
 
 // dw_debug_set key 7 (A/B): bit 0 LayerNorm-on-load off, bit 1 K/V append fusion off, bit 2 / bit 3: the self- / cross-attention of
@@ -34,8 +34,8 @@ int g_decode_fuse_off = 4;
 // tokens[b, 0:n] (decoder prompt included) takes v < 0 ? v * p : v / p, once however often it occurs -- and
 // NoRepeatNGramLogitsProcessor -- a column that would complete an n-gram the row already holds is excluded.  Both are
 // predicates on (column, row history) like the rest: the workgroup turns the <= 448 history tokens into two bitmaps in LDS
-// (one bit per column: `seen`, `banned`); a four-column chunk whose bits are all clear keeps the short path of `judge`.
-#define SEL_HIST_V 65536                            // bitmap capacity in columns (2 x 8 KB of LDS)
+// (one bit per column: `seen`, `banned`, select_rules.h); a four-column chunk whose bits are all clear keeps the short path of
+// `judge`.
 template <bool HIST>
 __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     const bf16* logits, int V, long ld, const uint8_t* suppress, const uint8_t* begin_suppress, int first, int no_eos,
@@ -52,33 +52,15 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
         return;
     }
     const bf16* row = logits + (long)b * ld;
-    if constexpr (HIST) {
-        for (int w = tid; w < SEL_HIST_V / 32; w += SEL_NT) { seen[w] = 0u; banned[w] = 0u; }
-        __syncthreads();
-        const int g = ngram;
-        for (int i = tid; i < n; i += SEL_NT) {
-            const long t = row_tok[i];
-            if (t < 0 || t >= V) continue;                                  // (no column: nothing to mark)
-            const unsigned bit = 1u << ((int)t & 31);
-            if (rep_pen != 1.0f) atomicOr(&seen[(int)t >> 5], bit);
-            if (g > 0 && i >= g - 1) {                                      // tokens[i] followed the window [i - g + 1, i)
-                bool hit = true;                                            // (n >= g here; g = 1: an empty window)
-                for (int k = 1; k < g && hit; ++k) hit = row_tok[i - k] == row_tok[n - k];
-                if (hit) atomicOr(&banned[(int)t >> 5], bit);
-            }
-        }
-        __syncthreads();
-    }
+    if constexpr (HIST) build_history_bitmaps(row_tok, n, V, rep_pen, ngram, seen, banned);
     auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
-    // row state of the timestamp rules and the allowed id intervals (select_rules.h)
     const RowRules rr = row_rules(row_tok, n, begin_index, tb, max_initial, V, eos, no_eos, redi);
-    const bool ts_mode = rr.ts_mode;
-    const int tsb = rr.tsb, tlo = rr.tlo, thi = rr.thi, slo = rr.slo, shi = rr.shi, ban_eos = rr.ban_eos, ban_nots = rr.ban_nots;
+    const int tsb = rr.tsb;
     auto allowed = [&](int c) -> bool {               // (used by the probability-mass pass below)
-        if (suppress && suppress[c]) return false;
-        if (first && begin_suppress && begin_suppress[c]) return false;
-        if constexpr (HIST) { if ((banned[c >> 5] >> (c & 31)) & 1u) return false; }
-        return ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots;
+        const unsigned masked = (suppress && suppress[c]) || (first && begin_suppress && begin_suppress[c]);
+        unsigned ban = 0;
+        if constexpr (HIST) ban = banned[c >> 5] >> (c & 31);
+        return column_allowed(rr, c, 0, V, masked, ban);
     };
     // ---- pass 1: best allowed text token and best allowed timestamp token ----
     // (the byte masks are fetched four columns at a time; the next chunk is requested before the current one is judged)
@@ -90,17 +72,11 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     // the short path -- a compare and two selects per column; ascending order within a thread makes the strict compare
     // keep the smallest index among equal values.
     auto judge = [&](int c0, const bf16x4& x, unsigned mask, bool live) {
-        const int c3 = c0 + 3;
-        const bool in_text = c0 >= tlo && c3 < thi, in_ts = c0 >= slo && c3 < shi;
-        bool clean = live && mask == 0 && c3 < V && (in_text || in_ts) && !(ban_eos >= c0 && ban_eos <= c3) &&
-                     !(ban_nots >= c0 && ban_nots <= c3);
-        unsigned sbits = 0, bbits = 0;                 // bit e: column c0 + e is in the history / banned (c0 is a multiple of 4)
-        if constexpr (HIST) {
-            sbits = (seen[c0 >> 5] >> (c0 & 31)) & 0xfu;
-            bbits = (banned[c0 >> 5] >> (c0 & 31)) & 0xfu;
-            clean = clean && (sbits | bbits) == 0;
-        }
-        if (clean) {
+        unsigned sbits = 0, bbits = 0;                 // bit e: column c0 + e is in the history / banned
+        if constexpr (HIST) { sbits = history_bits_of(seen, c0); bbits = history_bits_of(banned, c0); }
+        const ChunkKind kind = classify_chunk(rr, mask, live, c0, V, sbits, bbits);
+        if (kind.clean) {
+            const bool in_text = kind.in_text;
             float bv = in_text ? bt.v : bs.v;
             int bi = in_text ? bt.i : bs.i;
 #pragma unroll
@@ -114,10 +90,7 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int c = c0 + e;
-            const bool ok = live && c < V && !((mask >> (8 * e)) & 0xffu) &&
-                            ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots &&
-                            !((bbits >> e) & 1u);
-            if (ok) {
+            if (column_allowed(rr, c0, e, V, mask, bbits, live)) {
                 float v = bf2f(x[e]);
                 if constexpr (HIST) { if ((sbits >> e) & 1u) v = penal(v); }
                 const Best cand = {v, c};
@@ -149,7 +122,7 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     bt = block_best(bt, red);
     bs = block_best(bs, red);
     Best pick = better(bt, bs);
-    if (ts_mode && bs.v > -INFINITY) {
+    if (rr.ts_mode && bs.v > -INFINITY) {
         // sampled mass rule: if logsumexp over the allowed timestamps exceeds the best text logit, a timestamp is taken
         float sum = 0.f;
         for (int c = tsb + tid; c < V; c += SEL_NT)
@@ -183,11 +156,7 @@ extern "C" int dw_greedy_select(const void* logits, int B, int V, int64_t ld, co
                                 int fill, uint8_t* done, int64_t* cur, void* stream) {
     DW_CLEAR_ERR();
     if (!tokens || !cur || B <= 0 || n < 1 || n >= tok_ld) return DW_EINVAL;
-    if (!forced) {
-        if (!logits || V <= 0 || ld < V || (ld & 3) || ((uintptr_t)logits & 7)) return DW_EINVAL;
-        if (eos >= 0 && !done) return DW_EINVAL;
-        if (ts_begin >= 0 && (eos < 0 || begin_index < 1 || begin_index > n)) return DW_EINVAL;
-    }
+    if (!forced && (!select_args_ok(logits, V, ld, n, ts_begin, begin_index, eos) || (eos >= 0 && !done))) return DW_EINVAL;
     hipLaunchKernelGGL(greedy_select_kernel<false>, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V,
                        (long)ld, suppress, begin_suppress, first, no_eos, forced, ts_begin, max_initial, tokens,
                        (long)tok_ld, n, begin_index, eos, fill, done, cur, 1.0f, 0);
@@ -203,11 +172,7 @@ extern "C" int dw_greedy_select_history(const void* logits, int B, int V, int64_
     DW_CLEAR_ERR();
     if (!tokens || !cur || B <= 0 || n < 1 || n >= tok_ld) return DW_EINVAL;
     if (!(repetition_penalty > 0.f) || !(repetition_penalty <= 3.402823466e38f) || no_repeat_ngram < 0) return DW_EINVAL;
-    if (!forced) {
-        if (!logits || V <= 0 || V > SEL_HIST_V || ld < V || (ld & 3) || ((uintptr_t)logits & 7)) return DW_EINVAL;
-        if (eos >= 0 && !done) return DW_EINVAL;
-        if (ts_begin >= 0 && (eos < 0 || begin_index < 1 || begin_index > n)) return DW_EINVAL;
-    }
+    if (!forced && (!select_args_ok(logits, V, ld, n, ts_begin, begin_index, eos) || V > SEL_HIST_V || (eos >= 0 && !done))) return DW_EINVAL;
     hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V,
                        (long)ld, suppress, begin_suppress, first, no_eos, forced, ts_begin, max_initial, tokens,
                        (long)tok_ld, n, begin_index, eos, fill, done, cur, repetition_penalty, no_repeat_ngram);
@@ -324,29 +289,12 @@ __global__ __launch_bounds__(SEL_NT) void sample_select_kernel(
         return;
     }
     const bf16* row = logits + (long)b * ld;
-    // ---- history bitmaps and the row state of the timestamp rules: as in greedy_select_kernel<true> ----
-    for (int w = tid; w < SEL_HIST_V / 32; w += SEL_NT) { seen[w] = 0u; banned[w] = 0u; }
-    __syncthreads();
-    {
-        const int g = ngram;
-        for (int i = tid; i < n; i += SEL_NT) {
-            const long t = row_tok[i];
-            if (t < 0 || t >= V) continue;
-            const unsigned bit = 1u << ((int)t & 31);
-            if (rep_pen != 1.0f) atomicOr(&seen[(int)t >> 5], bit);
-            if (g > 0 && i >= g - 1) {
-                bool hit = true;
-                for (int k = 1; k < g && hit; ++k) hit = row_tok[i - k] == row_tok[n - k];
-                if (hit) atomicOr(&banned[(int)t >> 5], bit);
-            }
-        }
-    }
-    __syncthreads();
+    // ---- history bitmaps and the row state of the rules (select_rules.h), as in greedy_select_kernel<true> ----
+    build_history_bitmaps(row_tok, n, V, rep_pen, ngram, seen, banned);
     auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
-    // row state of the timestamp rules and the allowed id intervals (select_rules.h)
     const RowRules rr = row_rules(row_tok, n, begin_index, tb, max_initial, V, eos, no_eos, redi);
     const bool ts_mode = rr.ts_mode;
-    const int tsb = rr.tsb, tlo = rr.tlo, thi = rr.thi, slo = rr.slo, shi = rr.shi, ban_eos = rr.ban_eos, ban_nots = rr.ban_nots;
+    const int tsb = rr.tsb;
     // ---- 1. processed scores into registers: slot 4 i + e holds column tid * 4 + i * 4096 + e (-inf: excluded or beyond V) ----
     const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
     auto masks_of = [&](int c0) -> unsigned { return rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V); };
@@ -364,29 +312,22 @@ __global__ __launch_bounds__(SEL_NT) void sample_select_kernel(
         }
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
-            const int c0 = tid * 4 + i * SEL_NT * 4, c3 = c0 + 3;
+            const int c0 = tid * 4 + i * SEL_NT * 4;
             const bool live = c0 < V;
             const unsigned mask = mr[i];
-            const bool in_text = c0 >= tlo && c3 < thi, in_ts = c0 >= slo && c3 < shi;
             unsigned sbits = 0, bbits = 0;
-            if (live) {
-                sbits = (seen[c0 >> 5] >> (c0 & 31)) & 0xfu;
-                bbits = (banned[c0 >> 5] >> (c0 & 31)) & 0xfu;
-            }
-            const bool clean = live && mask == 0 && c3 < V && (in_text || in_ts) && !(ban_eos >= c0 && ban_eos <= c3) &&
-                               !(ban_nots >= c0 && ban_nots <= c3) && (sbits | bbits) == 0;
-            if (clean) {                               // the whole chunk inside one allowed interval, nothing masked or penalised
+            if (live) { sbits = history_bits_of(seen, c0); bbits = history_bits_of(banned, c0); }
+            const ChunkKind kind = classify_chunk(rr, mask, live, c0, V, sbits, bbits);
+            if (kind.clean) {                          // the whole chunk inside one allowed interval, nothing masked or penalised
                 float m = -INFINITY;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { s[4 * i + e] = bf2f(xr[i][e]); m = fmaxf(m, s[4 * i + e]); }
-                if (in_text) btv = fmaxf(btv, m); else bsv = fmaxf(bsv, m);
+                if (kind.in_text) btv = fmaxf(btv, m); else bsv = fmaxf(bsv, m);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int c = c0 + e;
-                    const bool ok = live && c < V && !((mask >> (8 * e)) & 0xffu) &&
-                                    ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots &&
-                                    !((bbits >> e) & 1u);
+                    const bool ok = column_allowed(rr, c0, e, V, mask, bbits, live);
                     float v = bf2f(xr[i][e]);
                     if ((sbits >> e) & 1u) v = penal(v);
                     v = ok ? v : -INFINITY;
@@ -403,18 +344,8 @@ __global__ __launch_bounds__(SEL_NT) void sample_select_kernel(
     // (a loop that compares its columns with a uniform bound takes its own copy of the bound through an empty asm: shared, or
     // hoisted out of the passes of a search, the 52 compare results would stay live in scalar registers and spill)
     auto fresh = [](auto x) { asm volatile("" : "+v"(x)); return x; };
-    auto block_max = [&](float x) -> float {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-        __syncthreads();
-        if ((tid & 63) == 0) redf[tid >> 6] = x;
-        __syncthreads();
-        float t = redf[0];
-        for (int i = 1; i < SEL_NT / 64; ++i) t = fmaxf(t, redf[i]);
-        return t;
-    };
-    btv = block_max(btv);
-    bsv = block_max(bsv);
+    btv = block_max<SEL_NT>(btv, redf);
+    bsv = block_max<SEL_NT>(bsv, redf);
     // the timestamp mass rule, as the greedy kernel decides it
     bool text_out = false;
     if (ts_mode && bsv > -INFINITY) {
@@ -564,9 +495,7 @@ extern "C" int dw_sample_select(const void* logits, int B, int V, int64_t ld, co
     DW_CLEAR_ERR();
     if (!tokens || !cur || B <= 0 || n < 1 || n >= tok_ld) return DW_EINVAL;
     if (!(repetition_penalty > 0.f) || !(repetition_penalty <= 3.402823466e38f) || no_repeat_ngram < 0) return DW_EINVAL;
-    if (!logits || V <= 0 || V > SEL_HIST_V || ld < V || (ld & 3) || ((uintptr_t)logits & 7)) return DW_EINVAL;
-    if (eos >= 0 && !done) return DW_EINVAL;
-    if (ts_begin >= 0 && (eos < 0 || begin_index < 1 || begin_index > n)) return DW_EINVAL;
+    if (!select_args_ok(logits, V, ld, n, ts_begin, begin_index, eos) || V > SEL_HIST_V || (eos >= 0 && !done)) return DW_EINVAL;
     if (!(temperature > 0.f) || !(temperature <= 3.402823466e38f) || top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f))
         return DW_EINVAL;
     if (!noise || noise_ld < V || ((uintptr_t)noise & 3)) return DW_EINVAL;

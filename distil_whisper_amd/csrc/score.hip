@@ -10,9 +10,10 @@
 // Here the sequences are already decoded: step j of row b is a function of tokens[b][0 .. P + j) and of the logits row of
 // position P - 1 + j, so every (step, row) pair is independent -- one 1024-thread workgroup each, no loop over steps.
 //
-// The rules, restated (they are the predicates of greedy_select_kernel in decode.hip, which picks the token during decoding;
-// tests/test_generate_scores_gpu.py pins the two kernels against each other).  With tsb = the first timestamp id and the history
-// h = tokens[b][P .. P + j) of the generated part:
+// The rules are those of the kernels that pick the token during decoding, and they are implemented once, in select_rules.h
+// (row_rules, rule_masks_of, column_allowed), with first = (j == 0), no_eos = (j < min_new) and begin_index = P;
+// tests/test_generate_scores_gpu.py pins this kernel against greedy_select_kernel.  In prose, with tsb = the first timestamp id
+// and the history h = tokens[b][P .. P + j) of the generated part:
 //   * EOS is masked while j < min_new;  begin_suppress masks its columns at j == 0 only;  suppress masks its columns always;
 //   * timestamp mode (ts_begin >= 0): <|notimestamps|> = tsb - 1 is masked always, and
 //       j == 0                     only timestamps, at most max_initial steps in:   allowed [tsb, tsb + max_initial]
@@ -31,10 +32,10 @@
 // reductions and its stores do not overlap with another's.  Plain kernel on the caller's stream: no allocation, no host
 // synchronisation.
 #include "common.h"
+#include "select_rules.h"                            // SEL_NT and the rules
 #include "../../include/dwamd.h"
 
-#define SC_NT 1024
-#define SC_NPRE 13                                   // chunks of SC_NT x 4 columns held in registers: 53 248 columns
+#define SC_NPRE 13                                   // chunks of SEL_NT x 4 columns held in registers: 53 248 columns
 
 struct ScoreP {
     const void* logits; long ld, batch_rows;
@@ -52,73 +53,32 @@ __device__ __forceinline__ f32x4 sc_ld4(const bf16* p) {
 __device__ __forceinline__ f32x4 sc_ld4(const float* p) { return *(const f32x4*)p; }
 
 template <class T>
-__global__ __launch_bounds__(SC_NT) void score_tokens_kernel(const ScoreP p) {
-    __shared__ float redf[SC_NT / 64];
-    __shared__ int redi[SC_NT / 64];
+__global__ __launch_bounds__(SEL_NT) void score_tokens_kernel(const ScoreP p) {
+    __shared__ float redf[SEL_NT / 64];
+    __shared__ int redi[SEL_NT / 64];
     const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int V = p.V, eos = p.eos;
     const int64_t* row_tok = p.tokens + (long)b * p.tok_ld;
     const int n = p.P + j;                          // position of the token this step chose
     const T* row = (const T*)p.logits + ((long)b * p.batch_rows + j) * p.ld;
+    const int first = j == 0;
+    const RowRules rr = row_rules(row_tok, n, p.P, p.tb, p.max_initial, V, eos, j < p.min_new, redi);
+    const bool ts_mode = rr.ts_mode;
+    const int tsb = rr.tsb;
     const uint8_t* suppress = p.suppress;
-    const uint8_t* begin_suppress = j == 0 ? p.begin_suppress : nullptr;
-    const bool ts_mode = p.tb >= 0;
-    const int tsb = ts_mode ? p.tb : V + 1;         // first timestamp id (beyond the vocabulary when the rules are off)
-    // ---- row state of the timestamp rules: from tokens[b][P .. n) ----
-    bool last_ts = false, pen_ts = true, any_ts = false;
-    int ts_last = 0;
-    if (ts_mode && j >= 1) {
-        last_ts = row_tok[n - 1] >= tsb;
-        pen_ts = j >= 2 ? row_tok[n - 2] >= tsb : true;
-        int pos = 0;                                // 1-based position (within the generated part) of the last timestamp
-        for (int i = tid; i < j; i += SC_NT) pos = row_tok[p.P + i] >= tsb ? max(pos, i + 1) : pos;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pos = max(pos, __shfl_xor(pos, o));
-        if ((tid & 63) == 0) redi[tid >> 6] = pos;
-        __syncthreads();
-        pos = 0;
-        for (int i = 0; i < SC_NT / 64; ++i) pos = max(pos, redi[i]);
-        any_ts = pos > 0;
-        if (any_ts) {
-            const int last_val = (int)row_tok[p.P + pos - 1];
-            ts_last = (last_ts && !pen_ts) ? last_val : last_val + 1;
-        }
-    }
-    // ---- the rules as two allowed id intervals, two single banned ids and the byte masks ----
-    int tlo = 0, thi = ts_mode ? tsb : V, slo = V, shi = V;        // allowed: [tlo, thi) and [slo, shi)
-    const int ban_eos = j < p.min_new ? eos : -1, ban_nots = ts_mode ? tsb - 1 : -1;
-    if (ts_mode) {
-        if (j >= 1) {
-            if (last_ts && pen_ts) { slo = shi = V; }                            // after a closed pair: text only
-            else {
-                slo = any_ts ? max(tsb, ts_last) : tsb;                           // timestamps never decrease
-                if (last_ts) tlo = eos;                                          // after text + timestamp: timestamp / EOS
-            }
-        } else {
-            tlo = thi = 0;                                                       // the first sampled token is a timestamp
-            slo = tsb;
-            shi = p.max_initial >= 0 ? min(V, tsb + p.max_initial + 1) : V;
-        }
-    }
+    const uint8_t* begin_suppress = first ? p.begin_suppress : nullptr;      // (so that word_masks asks nothing of an unused mask)
     const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
-    // bit e of the result: column c0 + e is allowed (c0 a multiple of 4; columns at or behind V are not)
+    // bit e of the result: column c0 + e is allowed (c0 a multiple of 4; columns at or behind V are not).  The condition is
+    // column_allowed of select_rules.h, written out: called as a function, its chain is turned into selects before it reaches this
+    // kernel, which then has 6 % more instructions and runs 1.4-3.7 % slower (profiles/select_rules_refactor.md).
     auto ok4 = [&](int c0) -> unsigned {
-        unsigned mask = 0;                           // byte e != 0: column c0 + e is suppressed
-        if (word_masks && c0 + 3 < V) {
-            if (suppress) mask |= *(const unsigned*)(suppress + c0);
-            if (begin_suppress) mask |= *(const unsigned*)(begin_suppress + c0);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (c0 + e < V && ((suppress && suppress[c0 + e]) || (begin_suppress && begin_suppress[c0 + e])))
-                    mask |= 0xffu << (8 * e);
-        }
+        const unsigned mask = rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V);
         unsigned ok = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int c = c0 + e;
-            const bool a = c < V && !((mask >> (8 * e)) & 0xffu) && ((c >= tlo && c < thi) || (c >= slo && c < shi)) &&
-                           c != ban_eos && c != ban_nots;
+            const bool a = c < V && !((mask >> (8 * e)) & 0xffu) && ((c >= rr.tlo && c < rr.thi) || (c >= rr.slo && c < rr.shi)) &&
+                           c != rr.ban_eos && c != rr.ban_nots;
             ok |= (a ? 1u : 0u) << e;
         }
         return ok;
@@ -131,7 +91,7 @@ __global__ __launch_bounds__(SC_NT) void score_tokens_kernel(const ScoreP p) {
     float tmax = NEG, smax = NEG;                    // best allowed text logit / best allowed timestamp logit
     bool mask_text = false;
     float M, sum = 0.f;
-    if (width <= SC_NPRE * SC_NT * 4) {
+    if (width <= SC_NPRE * SEL_NT * 4) {
         // ---- the row in registers: everything is requested before anything is judged ----
         // (chunk i starts at column i * 4096: a chunk wholly behind V is not loaded -- uniform over the workgroup; it holds
         // zeros that no allowed bit ever selects)
@@ -139,10 +99,10 @@ __global__ __launch_bounds__(SC_NT) void score_tokens_kernel(const ScoreP p) {
         unsigned long long okb = 0;                  // 4 bits per chunk
 #pragma unroll
         for (int i = 0; i < SC_NPRE; ++i)
-            xr[i] = i * SC_NT * 4 < V ? sc_ld4(row + min(tid * 4 + i * SC_NT * 4, clast)) : f32x4{0.f, 0.f, 0.f, 0.f};
+            xr[i] = i * SEL_NT * 4 < V ? sc_ld4(row + min(tid * 4 + i * SEL_NT * 4, clast)) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < SC_NPRE; ++i) {
-            const int c0 = tid * 4 + i * SC_NT * 4;
+            const int c0 = tid * 4 + i * SEL_NT * 4;
             const unsigned ok = c0 < V ? ok4(c0) : 0u;
             okb |= (unsigned long long)ok << (4 * i);
 #pragma unroll
@@ -151,24 +111,24 @@ __global__ __launch_bounds__(SC_NT) void score_tokens_kernel(const ScoreP p) {
                     if (c0 + e < tsb) tmax = fmaxf(tmax, xr[i][e]); else smax = fmaxf(smax, xr[i][e]);
                 }
         }
-        tmax = block_max<SC_NT>(tmax, redf);
-        smax = block_max<SC_NT>(smax, redf);
+        tmax = block_max<SEL_NT>(tmax, redf);
+        smax = block_max<SEL_NT>(smax, redf);
         if (ts_mode && smax > NEG) {
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < SC_NPRE; ++i) {
-                const int c0 = tid * 4 + i * SC_NT * 4;
+                const int c0 = tid * 4 + i * SEL_NT * 4;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (((okb >> (4 * i + e)) & 1ull) && c0 + e >= tsb) s += __expf(xr[i][e] - smax);
             }
-            s = block_sum<SC_NT>(s, redf);
+            s = block_sum<SEL_NT>(s, redf);
             mask_text = smax + __logf(s) > tmax;
         }
         M = mask_text ? smax : fmaxf(tmax, smax);
 #pragma unroll
         for (int i = 0; i < SC_NPRE; ++i) {
-            const int c0 = tid * 4 + i * SC_NT * 4;
+            const int c0 = tid * 4 + i * SEL_NT * 4;
             f32x4 y;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -180,7 +140,7 @@ __global__ __launch_bounds__(SC_NT) void score_tokens_kernel(const ScoreP p) {
         }
     } else {
         // ---- vocabularies beyond the register budget: the same three passes as loops over the row (L2 resident) ----
-        for (int c0 = tid * 4; c0 < V; c0 += SC_NT * 4) {
+        for (int c0 = tid * 4; c0 < V; c0 += SEL_NT * 4) {
             const f32x4 x = sc_ld4(row + c0);
             const unsigned ok = ok4(c0);
 #pragma unroll
@@ -189,22 +149,22 @@ __global__ __launch_bounds__(SC_NT) void score_tokens_kernel(const ScoreP p) {
                     if (c0 + e < tsb) tmax = fmaxf(tmax, x[e]); else smax = fmaxf(smax, x[e]);
                 }
         }
-        tmax = block_max<SC_NT>(tmax, redf);
-        smax = block_max<SC_NT>(smax, redf);
+        tmax = block_max<SEL_NT>(tmax, redf);
+        smax = block_max<SEL_NT>(smax, redf);
         if (ts_mode && smax > NEG) {
             float s = 0.f;
-            for (int c0 = (tsb & ~3) + tid * 4; c0 < V; c0 += SC_NT * 4) {
+            for (int c0 = (tsb & ~3) + tid * 4; c0 < V; c0 += SEL_NT * 4) {
                 const f32x4 x = sc_ld4(row + c0);
                 const unsigned ok = ok4(c0);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (((ok >> e) & 1u) && c0 + e >= tsb) s += __expf(x[e] - smax);
             }
-            s = block_sum<SC_NT>(s, redf);
+            s = block_sum<SEL_NT>(s, redf);
             mask_text = smax + __logf(s) > tmax;
         }
         M = mask_text ? smax : fmaxf(tmax, smax);
-        for (int c0 = tid * 4; c0 < width; c0 += SC_NT * 4) {
+        for (int c0 = tid * 4; c0 < width; c0 += SEL_NT * 4) {
             const f32x4 x = sc_ld4(row + min(c0, clast));
             const unsigned ok = c0 < V ? ok4(c0) : 0u;
             f32x4 y;
@@ -218,7 +178,7 @@ __global__ __launch_bounds__(SC_NT) void score_tokens_kernel(const ScoreP p) {
         }
     }
     if (!p.chosen && !p.logprob) return;             // (uniform)
-    sum = block_sum<SC_NT>(sum, redf);
+    sum = block_sum<SEL_NT>(sum, redf);
     if (tid == 0) {
         const long tok = row_tok[n];
         float sc = NEG, lp = NEG;
@@ -249,7 +209,7 @@ extern "C" int dw_score_tokens(const void* logits, int dtype, int B, int L, int 
     p.suppress = suppress; p.begin_suppress = begin_suppress;
     p.scores = scores; p.ld_scores = (long)ld_scores; p.chosen = chosen; p.logprob = logprob;
     p.B = B; p.L = L; p.V = V; p.P = begin_index; p.min_new = min_new; p.tb = ts_begin; p.max_initial = max_initial; p.eos = eos;
-    const dim3 grid(L, B), block(SC_NT);
+    const dim3 grid(L, B), block(SEL_NT);
     if (dtype == DW_F32) hipLaunchKernelGGL(score_tokens_kernel<float>, grid, block, 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(score_tokens_kernel<bf16>, grid, block, 0, (hipStream_t)stream, p);
     DW_CHECK_LAUNCH();

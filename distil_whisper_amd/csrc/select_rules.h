@@ -1,11 +1,15 @@
-// Device code shared by the token-selection kernels (decode.hip: greedy / history / sampled selection; beam.hip: beam-search
-// candidates): the workgroup shape, the (value, index) reduction, and the row state of the reference's logits rules
-// (MinNewTokensLength, SuppressTokens, SuppressTokensAtBegin and WhisperTimeStampLogitsProcessor, TF:generation/logits_process.py)
-// as two allowed id intervals plus two single banned ids.
+// The one statement of the reference's logits rules (MinNewTokensLength, SuppressTokens, SuppressTokensAtBegin and
+// WhisperTimeStampLogitsProcessor, TF:generation/logits_process.py; RepetitionPenalty / NoRepeatNGram as history bitmaps) for the
+// kernels that apply them -- decode.hip: greedy / history / sampled selection; beam.hip: beam-search candidates; score.hip: scores
+// of finished sequences -- with the workgroup shape and the (value, index) reduction they share.  A rule changes here and
+// nowhere else: the row state as two allowed id intervals plus two single banned ids (row_rules), the byte masks
+// (rule_masks_of), the history bitmaps (build_history_bitmaps), the clean-chunk test (classify_chunk) and the per-column
+// predicate (column_allowed).  What the kernels keep to themselves is arithmetic: how they hold a row and in which order they sum.
 #pragma once
 #include "common.h"
 
 #define SEL_NT 1024
+#define SEL_HIST_V 65536                            // capacity of a history bitmap in columns (8 KB of LDS each)
 
 struct Best { float v; int i; };
 __device__ __forceinline__ Best better(Best a, Best b) {      // larger value wins, ties go to the smaller index
@@ -28,13 +32,10 @@ __device__ __forceinline__ Best block_best(Best x, Best* red) {
 
 // Every rule is a predicate on the column alone once the row state is known: column c may be selected iff it lies in
 // [tlo, thi) (text / special ids below the first timestamp) or [slo, shi) (timestamp ids), is neither ban_eos nor ban_nots,
-// and no byte mask names it.  tsb: first timestamp id (beyond the vocabulary when the timestamp rules are off).
+// and no byte mask names it (column_allowed below).  tsb: first timestamp id (beyond the vocabulary when the timestamp rules are off).
 struct RowRules {
     bool ts_mode;
     int tsb, tlo, thi, slo, shi, ban_eos, ban_nots;
-    __device__ __forceinline__ bool in_range(int c) const {
-        return ((c >= tlo && c < thi) || (c >= slo && c < shi)) && c != ban_eos && c != ban_nots;
-    }
 };
 
 // Called by all SEL_NT threads of the workgroup (it synchronises when the timestamp rules are on).  row_tok: the row's sequence,
@@ -102,4 +103,62 @@ __device__ __forceinline__ unsigned rule_masks_of(const uint8_t* suppress, const
                 mask |= 0xffu << (8 * e);
     }
     return mask;
+}
+
+// The history bitmaps of RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor, one bit per column, from the history
+// row_tok[0, n) (decoder prompt included): `seen` -- the id occurs (built only when rep_pen != 1); `banned` -- the id would
+// complete an n-gram of length `ngram` that the row already holds (ngram = 0: off).  Called by all SEL_NT threads; both bitmaps
+// are SEL_HIST_V / 32 words of LDS, complete on return.
+__device__ __forceinline__ void build_history_bitmaps(const int64_t* row_tok, int n, int V, float rep_pen, int ngram, unsigned* seen,
+                                                      unsigned* banned) {
+    const int tid = threadIdx.x;
+    for (int w = tid; w < SEL_HIST_V / 32; w += SEL_NT) { seen[w] = 0u; banned[w] = 0u; }
+    __syncthreads();
+    const int g = ngram;
+    for (int i = tid; i < n; i += SEL_NT) {
+        const long t = row_tok[i];
+        if (t < 0 || t >= V) continue;                                  // (no column: nothing to mark)
+        const unsigned bit = 1u << ((int)t & 31);
+        if (rep_pen != 1.0f) atomicOr(&seen[(int)t >> 5], bit);
+        if (g > 0 && i >= g - 1) {                                      // tokens[i] followed the window [i - g + 1, i)
+            bool hit = true;                                            // (n >= g here; g = 1: an empty window)
+            for (int k = 1; k < g && hit; ++k) hit = row_tok[i - k] == row_tok[n - k];
+            if (hit) atomicOr(&banned[(int)t >> 5], bit);
+        }
+    }
+    __syncthreads();
+}
+// bit e: column c0 + e is set in the bitmap (c0 a multiple of 4, below SEL_HIST_V)
+__device__ __forceinline__ unsigned history_bits_of(const unsigned* bitmap, int c0) { return (bitmap[c0 >> 5] >> (c0 & 31)) & 0xfu; }
+
+// The four columns c0 .. c0 + 3 (c0 a multiple of 4) as a whole.  clean: all four exist (`live`: the chunk is no clamped repeat
+// of the row's last one), lie inside ONE allowed interval, and no mask byte, banned id or history bit (sbits / bbits of
+// history_bits_of: seen / banned; 0 without history rules) names any of them -- each column then keeps its logit and counts as
+// text (in_text) or timestamp.  A chunk that is not clean is judged column by column with column_allowed.
+struct ChunkKind { bool clean, in_text; };
+__device__ __forceinline__ ChunkKind classify_chunk(const RowRules& r, unsigned mask, bool live, int c0, int V, unsigned sbits = 0,
+                                                    unsigned bbits = 0) {
+    const int c3 = c0 + 3;
+    const bool in_text = c0 >= r.tlo && c3 < r.thi, in_ts = c0 >= r.slo && c3 < r.shi;
+    const bool inside = live && mask == 0 && c3 < V && (in_text || in_ts) && !(r.ban_eos >= c0 && r.ban_eos <= c3) &&
+                        !(r.ban_nots >= c0 && r.ban_nots <= c3);
+    return {inside && (sbits | bbits) == 0, in_text};
+}
+
+// Column c = c0 + e may be selected: it exists (c < V, and `live`: its chunk is no clamped repeat of the row's last one), byte e
+// of `mask` (rule_masks_of) is clear, the row state allows it, and bit e of `bbits` (history_bits_of(banned); 0 without history
+// rules) is clear.  For one column on its own: e = 0 with its byte and bit.  (The whole condition in one chain on purpose: as the
+// tail of a caller's `live && c < V && ...` greedy_select_kernel<true> ran 0.2-0.4 us slower, profiles/select_rules_refactor.md.)
+__device__ __forceinline__ bool column_allowed(const RowRules& r, int c0, int e, int V, unsigned mask, unsigned bbits = 0,
+                                               bool live = true) {
+    const int c = c0 + e;
+    return live && c < V && !((mask >> (8 * e)) & 0xffu) && ((c >= r.tlo && c < r.thi) || (c >= r.slo && c < r.shi)) &&
+           c != r.ban_eos && c != r.ban_nots && !((bbits >> e) & 1u);
+}
+
+// Host side, for the C entries of these kernels (the one header they share): what every entry asks of the logits rows and of
+// the arguments of the timestamp rules (true: accept).  n: the position the step fills.
+static inline bool select_args_ok(const void* logits, int V, int64_t ld, int n, int ts_begin, int begin_index, int eos) {
+    if (!logits || V <= 0 || ld < V || (ld & 3) || ((uintptr_t)logits & 7)) return false;
+    return !(ts_begin >= 0 && (eos < 0 || begin_index < 1 || begin_index > n));
 }

@@ -107,6 +107,15 @@ def warp_and_sample(scores, temperature=None, top_k=None, top_p=None, generator=
     return torch.multinomial(probs, num_samples=1, generator=generator)[:, 0]
 
 
+def rule_kwargs(timestamp_rules, eos):
+    """The keyword arguments by which the token-selection entries of `ops` take the timestamp rules (the dict given to
+    GreedyDecoder, or None) and the EOS id (None: no EOS bookkeeping)."""
+    r = timestamp_rules
+    mi = None if r is None else r.get("max_initial_timestamp_index")
+    return dict(ts_begin=-1 if r is None else r["no_timestamps_token_id"] + 1, max_initial=-1 if mi is None else mi,
+                begin_index=1 if r is None else r["begin_index"], eos=-1 if eos is None else eos)
+
+
 class GreedyDecoder:
     def __init__(self, engine, batch, max_len, eos_token_id=None, suppress_tokens=None, begin_suppress_tokens=None,
                  use_graphs=None, check_every=16, timestamp_rules=None, pad_token_id=None, soft=None):
@@ -177,34 +186,21 @@ class GreedyDecoder:
         eng, d = self.eng, self.eng.dims
         self.cache["t"] = t
         logits = eng.decode_step(self.cur, self.cache)
-        r = self.timestamp_rules
         if self.soft is not None and self.history is None and self.sample is None and mode != 0:
             self._select_soft(logits, t + 1, mode, no_eos)
             return
+        # logits processors of the reference (min-new-tokens, begin-suppress, suppress, timestamp rules), the choice of the
+        # token and the EOS bookkeeping in one launch (csrc/decode.hip); the next token lands in tokens[:, t+1] and in cur
+        ops, args = eng.ops, (logits, d.vocab, self.tokens, t + 1, self.cur)
+        common = dict(suppress=self.suppress, begin_suppress=self.begin_suppress, first=(mode == 1), no_eos=no_eos,
+                      fill=self.fill, done=self.done, **rule_kwargs(self.timestamp_rules, self.eos))
         if self.sample is not None and mode != 0:
             # (`noise` holds this position's draw: `_run_step` filled it just before this launch / this graph's replay)
-            eng.ops.sample_select(
-                logits, d.vocab, self.tokens, t + 1, self.cur, self.noise, suppress=self.suppress,
-                begin_suppress=self.begin_suppress, first=(mode == 1), no_eos=no_eos,
-                ts_begin=-1 if r is None else r["no_timestamps_token_id"] + 1,
-                max_initial=-1 if (r is None or r.get("max_initial_timestamp_index") is None)
-                else r["max_initial_timestamp_index"],
-                begin_index=1 if r is None else r["begin_index"], eos=-1 if self.eos is None else self.eos,
-                fill=self.fill, done=self.done, **self.sample)
-            return
-        # logits processors of the reference (min-new-tokens, begin-suppress, suppress, timestamp rules), argmax and the
-        # EOS bookkeeping in one launch (csrc/decode.hip); the next token lands in tokens[:, t+1] and in cur
-        select, hist = eng.ops.greedy_select, {}
-        if self.history is not None:
-            select, hist = eng.ops.greedy_select_history, self.history
-        select(
-            logits, d.vocab, self.tokens, t + 1, self.cur, suppress=self.suppress, begin_suppress=self.begin_suppress,
-            first=(mode == 1), no_eos=no_eos, forced=(mode == 0),
-            ts_begin=-1 if r is None else r["no_timestamps_token_id"] + 1,
-            max_initial=-1 if (r is None or r.get("max_initial_timestamp_index") is None)
-            else r["max_initial_timestamp_index"],
-            begin_index=1 if r is None else r["begin_index"], eos=-1 if self.eos is None else self.eos,
-            fill=self.fill, done=self.done, **hist)
+            ops.sample_select(*args, self.noise, **common, **self.sample)
+        elif self.history is not None:
+            ops.greedy_select_history(*args, forced=(mode == 0), **common, **self.history)
+        else:
+            ops.greedy_select(*args, forced=(mode == 0), **common)
 
     def _select_soft(self, logits, n, mode, no_eos):
         """Token n of every row from `logits` with the history-dependent processors / sampling of `self.soft`."""
@@ -560,7 +556,6 @@ def beam_search_decode(engine, enc_out, prompt_ids, max_new_tokens, num_beams, e
 
     if use_kernels:
         sup, bsup = mask_of(suppress_tokens, torch.uint8), mask_of(begin_suppress_tokens, torch.uint8)
-        tr = timestamp_rules
         R = B * nb
         other = dict(running=torch.full_like(running, fill), sequences=torch.full_like(running, fill))
         other["running"][:, :, :P] = prompt_ids[:, None, :]
@@ -575,10 +570,7 @@ def beam_search_decode(engine, enc_out, prompt_ids, max_new_tokens, num_beams, e
             ops.beam_candidates(
                 logits, V, st["running"].view(R, max_length), cur, st["run_scores"], cand_val, cand_tok, stop, suppress=sup,
                 begin_suppress=bsup, first=(cur == P), no_eos=(cur - P) < int(min_new_tokens),
-                ts_begin=-1 if tr is None else tr["no_timestamps_token_id"] + 1,
-                max_initial=-1 if (tr is None or tr.get("max_initial_timestamp_index") is None)
-                else tr["max_initial_timestamp_index"],
-                begin_index=1 if tr is None else tr["begin_index"], eos=eos)
+                **rule_kwargs(timestamp_rules, eos))
             fin_div, hyp_div = divisors(cur)
             ops.beam_update(cand_val, cand_tok, B, nb, V, cur, P, max_length, eos, early_stopping, fin_div, hyp_div,
                             st["running"], other["running"], st["sequences"], other["sequences"], st["run_scores"],

@@ -627,17 +627,23 @@ class HipOps:
         self._chk(self.lib.dw_sumsq_f32(_p(g), g.numel(), _p(out), _p(self._sumsq_ws), self._stream()), "sumsq")
         return out
 
+    @staticmethod
+    def _check_select(logits, rows, V, suppress, begin_suppress, tokens=None, cur=None, done=None):
+        """What the token-selection wrappers ask of their common arguments (logits None: a forced step, they are not read)."""
+        if logits is not None:
+            assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= rows
+        for m in (suppress, begin_suppress):
+            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
+        if cur is not None:
+            assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous()
+        assert done is None or (done.dtype == torch.bool and done.is_contiguous())
+
     def greedy_select(self, logits, V, tokens, n, cur, *, suppress=None, begin_suppress=None, first=False, no_eos=False,
                       forced=False, ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, fill=-1, done=None):
         """One decoding step's token selection for the whole batch (csrc/decode.hip): logits bf16 [B, ld] -> next token
         written to tokens[:, n] and cur[:, 0]; masks are uint8 [V] (1 = never sampled); done bool [B] in/out."""
         B = tokens.shape[0]
-        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous()
-        if not forced:
-            assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= B
-        for m in (suppress, begin_suppress):
-            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
-        assert done is None or (done.dtype == torch.bool and done.is_contiguous())
+        self._check_select(None if forced else logits, B, V, suppress, begin_suppress, tokens, cur, done)
         self._chk(self.lib.dw_greedy_select(_p(logits), B, int(V), logits.stride(0) if logits is not None else 0,
                                             _p(suppress), _p(begin_suppress), int(first), int(no_eos), int(forced),
                                             int(ts_begin), int(max_initial), _p(tokens), tokens.stride(0), int(n),
@@ -650,12 +656,7 @@ class HipOps:
         """`greedy_select` with GenerationMixin's repetition penalty and no-repeat-n-gram rule in front of the other rules, in
         the same single launch: the history of row b is tokens[b, :n] (decoder prompt included)."""
         B = tokens.shape[0]
-        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous()
-        if not forced:
-            assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= B
-        for m in (suppress, begin_suppress):
-            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
-        assert done is None or (done.dtype == torch.bool and done.is_contiguous())
+        self._check_select(None if forced else logits, B, V, suppress, begin_suppress, tokens, cur, done)
         self._chk(self.lib.dw_greedy_select_history(
             _p(logits), B, int(V), logits.stride(0) if logits is not None else 0, _p(suppress), _p(begin_suppress),
             int(first), int(no_eos), int(forced), int(ts_begin), int(max_initial), _p(tokens), tokens.stride(0), int(n),
@@ -669,12 +670,8 @@ class HipOps:
         the draw argmax softmax(s) / noise.  noise f32 [B, >= V]: `noise.exponential_(1.0, generator=g)` makes the token the one
         `torch.multinomial(softmax(s), 1, generator=g)` draws."""
         B = tokens.shape[0]
-        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous()
-        assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= B
+        self._check_select(logits, B, V, suppress, begin_suppress, tokens, cur, done)
         assert noise.dtype == torch.float32 and noise.stride(1) == 1 and noise.shape[0] >= B and noise.shape[1] >= V
-        for m in (suppress, begin_suppress):
-            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
-        assert done is None or (done.dtype == torch.bool and done.is_contiguous())
         self._chk(self.lib.dw_sample_select(
             _p(logits), B, int(V), logits.stride(0), _p(suppress), _p(begin_suppress), int(first), int(no_eos), int(ts_begin),
             int(max_initial), _p(tokens), tokens.stride(0), int(n), int(begin_index), int(eos), int(fill), _p(done), _p(cur),
@@ -695,14 +692,12 @@ class HipOps:
         over the columns the rules of `greedy_select` allow, value descending, then column ascending.  stop int32 [1]: non-zero
         = nothing is written."""
         R, K = cand_val.shape
-        assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= R
+        self._check_select(logits, R, V, suppress, begin_suppress)
         assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[0] >= R and tokens.shape[1] >= n
         assert run_scores.dtype == torch.float32 and run_scores.is_contiguous() and run_scores.numel() == R
         assert cand_val.dtype == torch.float32 and cand_val.is_contiguous()
         assert cand_tok.dtype == torch.int32 and cand_tok.is_contiguous() and cand_tok.shape == cand_val.shape
         assert stop.dtype == torch.int32 and stop.numel() == 1
-        for m in (suppress, begin_suppress):
-            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
         self._chk(self.lib.dw_beam_candidates(
             _p(logits), R, int(V), logits.stride(0), _p(suppress), _p(begin_suppress), int(first), int(no_eos), int(ts_begin),
             int(max_initial), _p(tokens), tokens.stride(0), int(n), int(begin_index), int(eos), _p(run_scores), K, _p(cand_val),
