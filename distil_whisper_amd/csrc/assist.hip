@@ -1,0 +1,200 @@
+// Speculative (assisted) greedy decoding, the two launches of a round that are not decoder passes.
+//
+// Reference behaviour (third-party `transformers`, TF: = transformers/generation/): `_assisted_decoding` (TF:utils.py) with the
+// greedy branch of `_speculative_sampling`'s caller -- the assistant drafts k tokens one at a time through the target's logits
+// processors (TF:candidate_generator.py `AssistedCandidateGenerator.get_candidates`), the target scores the k + 1 positions in one
+// pass, `n_matches = ((~(candidate_new_tokens == selected_tokens[:, :-1])).cumsum(-1) < 1).sum()` and the sequence grows by the
+// matching drafts plus the target's own next token; reached from run_eval.py:578-599, 706-707 (`assistant_model=`).  What the
+// host loop of decoding.assisted_greedy_decode did with a dozen torch ops and two synchronisations per round:
+//
+//   dw_assist_pick    the token the logits rules select at n consecutive positions of every row -- greedy_select_kernel<false>
+//                     (decode.hip) without its EOS bookkeeping and over a (position, row) grid like score_tokens_kernel
+//                     (score.hip).  Position j of row b is judged against the history tokens[b][0, L + j): for j > 0 that
+//                     history holds the drafts, which the draft steps stored before this launch, so the n positions of a row are
+//                     independent workgroups.  The rules are those of select_rules.h (row_rules, rule_masks_of, classify_chunk,
+//                     column_allowed); this file holds none of its own.
+//   dw_assist_accept  the round's bookkeeping for the whole batch in one workgroup, one thread per row: the length of the
+//                     agreeing draft prefix, its minimum over the rows, the accepted tokens with the finished rows filled.
+//
+// Both are plain kernels on the caller's stream: nothing is allocated, nothing synchronises, no workgroup waits for another.
+// Cost model of the pick: as greedy_select_kernel, a row lives on one CU and is bound by instructions per column (13 chunks of
+// four columns per thread at V = 51 866, all requested before any is judged); n x B rows run side by side on the 256 CUs.
+#include "common.h"
+#include "select_rules.h"                           // SEL_NT, Best / block_best and every logits rule
+#include "../../include/dwamd.h"
+
+struct AssistPickP {
+    const bf16* logits; long ld, batch_rows;
+    const uint8_t* suppress; const uint8_t* begin_suppress;
+    int64_t* tokens; long tok_ld;
+    int64_t* own; long own_ld;
+    int64_t* cur;
+    int V, L, P0, min_new, tb, max_initial, eos, store;
+};
+
+__global__ __launch_bounds__(SEL_NT) void assist_pick_kernel(const AssistPickP p) {
+    __shared__ Best red[SEL_NT / 64];
+    __shared__ float redf[SEL_NT / 64];
+    __shared__ int redi[SEL_NT / 64];
+    const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int V = p.V;
+    int64_t* row_tok = p.tokens + (long)b * p.tok_ld;
+    const int n = p.L + j;                          // the sequence index this workgroup fills
+    const bf16* row = p.logits + ((long)b * p.batch_rows + j) * p.ld;
+    const int first = n == p.P0;
+    const uint8_t* suppress = p.suppress;
+    const uint8_t* begin_suppress = first ? p.begin_suppress : nullptr;      // (so that word_masks asks nothing of an unused mask)
+    const RowRules rr = row_rules(row_tok, n, p.P0, p.tb, p.max_initial, V, p.eos, (n - p.P0) < p.min_new, redi);
+    const int tsb = rr.tsb;
+    const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
+    auto masks_of = [&](int c0) -> unsigned { return rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V); };
+    // ---- pass 1: best allowed text token and best allowed timestamp token (the chunk walk of greedy_select_kernel) ----
+    Best bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
+    auto judge = [&](int c0, const bf16x4& x, unsigned mask, bool live) {
+        const ChunkKind kind = classify_chunk(rr, mask, live, c0, V);
+        if (kind.clean) {                              // ascending order within a thread: the strict compare keeps the first of equals
+            const bool in_text = kind.in_text;
+            float bv = in_text ? bt.v : bs.v;
+            int bi = in_text ? bt.i : bs.i;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float v = bf2f(x[e]);
+                if (v > bv) { bv = v; bi = c0 + e; }
+            }
+            if (in_text) { bt.v = bv; bt.i = bi; } else { bs.v = bv; bs.i = bi; }
+            return;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = c0 + e;
+            if (column_allowed(rr, c0, e, V, mask, 0u, live)) {
+                const Best cand = {bf2f(x[e]), c};
+                if (c < tsb) bt = better(bt, cand); else bs = better(bs, cand);
+            }
+        }
+    };
+    constexpr int NPRE = 13;                           // 13 x 4096 columns cover every Whisper vocabulary (51 866)
+    if (V <= NPRE * SEL_NT * 4) {
+        // the whole row is requested before anything is judged, with clamped addresses instead of branches around the loads
+        const int clast = (V - 1) & ~3;
+        bf16x4 xr[NPRE];
+        unsigned mr[NPRE];
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) {
+            const int c0 = min(tid * 4 + i * SEL_NT * 4, clast);
+            xr[i] = *(const bf16x4*)(row + c0);
+            mr[i] = masks_of(c0);
+        }
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) {
+            const int c0 = tid * 4 + i * SEL_NT * 4;
+            judge(min(c0, clast), xr[i], mr[i], c0 < V);
+        }
+    } else {
+        for (int c0 = tid * 4; c0 < V; c0 += SEL_NT * 4) judge(c0, *(const bf16x4*)(row + c0), masks_of(c0), true);
+    }
+    bt = block_best(bt, red);
+    bs = block_best(bs, red);
+    Best pick = better(bt, bs);
+    if (rr.ts_mode && bs.v > -INFINITY) {
+        // mass rule: if logsumexp over the allowed timestamps exceeds the best text logit, a timestamp is taken
+        float sum = 0.f;
+        for (int c = tsb + tid; c < V; c += SEL_NT) {
+            const unsigned masked = (suppress && suppress[c]) || (begin_suppress && begin_suppress[c]);
+            if (column_allowed(rr, c, 0, V, masked)) sum += __expf(bf2f(row[c]) - bs.v);
+        }
+        sum = wave_sum(sum);
+        __syncthreads();
+        if ((tid & 63) == 0) redf[tid >> 6] = sum;
+        __syncthreads();
+        sum = 0.f;
+        for (int i = 0; i < SEL_NT / 64; ++i) sum += redf[i];
+        if (bs.v + __logf(sum) > bt.v) pick = bs;
+    }
+    if (tid == 0) {
+        const long nxt = pick.i == 0x7fffffff ? 0 : pick.i;
+        p.own[(long)b * p.own_ld + j] = nxt;
+        if (p.store) {                              // the assistant's draft step (n == 1): the next pass reads it
+            row_tok[n] = nxt;
+            p.cur[b] = nxt;
+        }
+    }
+}
+
+extern "C" int dw_assist_pick(const void* logits, int B, int n, int V, int64_t ld, int64_t batch_rows, const uint8_t* suppress,
+                              const uint8_t* begin_suppress, int min_new, int ts_begin, int max_initial, int64_t* tokens,
+                              int64_t tok_ld, int L, int begin_index, int eos, int64_t* own, int64_t own_ld, int store,
+                              int64_t* cur, void* stream) {
+    DW_CLEAR_ERR();
+    if (!tokens || !own || B <= 0 || B > 65535 || n <= 0 || L < 1 || begin_index < 1 || begin_index > L) return DW_EINVAL;
+    if (batch_rows < n || own_ld < n || tok_ld < (int64_t)L + n - (store ? 0 : 1) || min_new < 0 || eos >= V) return DW_EINVAL;
+    if (store && (n != 1 || !cur)) return DW_EINVAL;
+    if (!select_args_ok(logits, V, ld, L, ts_begin, begin_index, eos)) return DW_EINVAL;
+    AssistPickP p;
+    p.logits = (const bf16*)logits; p.ld = (long)ld; p.batch_rows = (long)batch_rows;
+    p.suppress = suppress; p.begin_suppress = begin_suppress;
+    p.tokens = tokens; p.tok_ld = (long)tok_ld; p.own = own; p.own_ld = (long)own_ld; p.cur = cur;
+    p.V = V; p.L = L; p.P0 = begin_index; p.min_new = min_new; p.tb = ts_begin; p.max_initial = max_initial; p.eos = eos;
+    p.store = store;
+    hipLaunchKernelGGL(assist_pick_kernel, dim3(n, B), dim3(SEL_NT), 0, (hipStream_t)stream, p);
+    DW_CHECK_LAUNCH();
+    return DW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// dw_assist_accept: thread b owns row b.  m_b = the leading drafts tokens[b][L + j], j < k, that equal own[b][j] (k for a
+// finished row); n_ok = the minimum over the rows; then, in order, tokens[b][L + j] = done[b] ? fill : own[b][j] and
+// done[b] |= that token == eos for j <= n_ok.  Rows and k are a few; the launch is latency, not work.
+// ---------------------------------------------------------------------------------------------------------------------
+#define ASSIST_MAX_B 1024
+#define ASSIST_MAX_K 1024
+
+__global__ __launch_bounds__(ASSIST_MAX_B) void assist_accept_kernel(const int64_t* own, long own_ld, int64_t* tokens, long tok_ld,
+                                                                     int B, int L, int k, int eos, int fill, uint8_t* done,
+                                                                     int32_t* result) {
+    __shared__ int s_min, s_live;
+    const int b = threadIdx.x;
+    if (b == 0) { s_min = k; s_live = 0; }
+    __syncthreads();
+    const bool row = b < B;
+    const int64_t* o = own + (long)b * own_ld;
+    int64_t* t = tokens + (long)b * tok_ld + L;
+    bool fin = false;
+    if (row) {
+        fin = eos >= 0 && done[b];
+        int m = k;
+        if (!fin) {
+            m = 0;
+            while (m < k && o[m] == t[m]) ++m;
+        }
+        if (m < k) atomicMin(&s_min, m);
+    }
+    __syncthreads();
+    const int n_ok = s_min;
+    if (row) {
+        for (int j = 0; j <= n_ok; ++j) {
+            const int64_t c = fin ? (int64_t)fill : o[j];
+            t[j] = c;
+            if (eos >= 0 && c == eos) fin = true;
+        }
+        if (eos >= 0) done[b] = fin ? 1 : 0;
+        if (!fin) atomicOr(&s_live, 1);
+    }
+    __syncthreads();
+    if (b == 0) {
+        result[0] = n_ok;
+        result[1] = (eos >= 0 && !s_live) ? 1 : 0;
+    }
+}
+
+extern "C" int dw_assist_accept(const int64_t* own, int64_t own_ld, int64_t* tokens, int64_t tok_ld, int B, int L, int k, int eos,
+                                int fill, uint8_t* done, int32_t* result, void* stream) {
+    DW_CLEAR_ERR();
+    if (!own || !tokens || !result || B <= 0 || L < 1 || k < 0 || (eos >= 0 && !done)) return DW_EINVAL;
+    if (B > ASSIST_MAX_B || k > ASSIST_MAX_K) return DW_EUNSUP;
+    if (own_ld < (int64_t)k + 1 || tok_ld < (int64_t)L + k + 1) return DW_EINVAL;
+    hipLaunchKernelGGL(assist_accept_kernel, dim3(1), dim3((B + 63) / 64 * 64), 0, (hipStream_t)stream, own, (long)own_ld, tokens,
+                       (long)tok_ld, B, L, k, eos, fill, done, result);
+    DW_CHECK_LAUNCH();
+    return DW_OK;
+}

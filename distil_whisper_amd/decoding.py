@@ -280,6 +280,55 @@ class GreedyDecoder:
         return self.tokens[:, :n].clone()
 
 
+# DW_ASSIST_TORCH=1 (read when an assisted decode starts): the round stays on the torch ops of `assist_pick_torch` / `assist_accept_torch`
+# on every engine, as on ops without `assist_pick` / `assist_accept` -- the A/B leg of tools/bench_assist.py and the reference leg of
+# tests/test_assist_gpu.py
+ASSIST_TORCH_ENV = "DW_ASSIST_TORCH"
+
+
+def assist_pick_torch(logits, hist, first_pos, begin_index, eos_token_id=None, min_new_tokens=0, suppress=None,
+                      timestamp_rules=None):
+    """Greedy tokens int64 [B, n] from scores [B, n, V] whose row j predicts the token at sequence index first_pos + j (the torch
+    path of oracle.ref_ops, of CPU runs, of unsupported sizes and of DW_ASSIST_TORCH=1; csrc/assist.hip `dw_assist_pick` is the
+    kernel).  hist int64 [B, >= first_pos + n - 1]: the sequence those positions continue (history of the timestamp rules);
+    begin_index: decoder prompt length; suppress: f32 [V] with -inf at the suppressed ids, or None."""
+    sc = logits.float()
+    dev = sc.device
+    V = sc.shape[-1]
+    if suppress is not None:
+        sc = sc + suppress
+    if eos_token_id is not None and min_new_tokens > 0 and eos_token_id < V:
+        gen_idx = torch.arange(first_pos - begin_index, first_pos - begin_index + sc.shape[1], device=dev)
+        sc = sc.clone()
+        sc[:, :, eos_token_id] = torch.where((gen_idx < min_new_tokens)[None, :], float("-inf"),
+                                             sc[:, :, eos_token_id])
+    if timestamp_rules is not None:
+        tr = timestamp_rules
+        sc = torch.stack([apply_timestamp_rules(sc[:, j], hist, first_pos + j, int(tr["begin_index"]),
+                                                int(tr["no_timestamps_token_id"]), eos_token_id,
+                                                tr.get("max_initial_timestamp_index"))
+                          for j in range(sc.shape[1])], 1)
+    return sc.argmax(-1)
+
+
+def assist_accept_torch(own, draft, L, k, done, eos_token_id, fill):
+    """The bookkeeping of one round as torch ops (`dw_assist_accept` is the kernel): own int64 [B, k + 1] the target's choices at
+    positions L .. L + k, draft int64 [B, L + k] the sequence with the k drafts, done bool [B].  Returns (new int64 [B, n_ok + 1]:
+    the accepted drafts -- equal to own -- plus the target's next token, finished rows filled; done; n_ok)."""
+    if k > 0:
+        agree = (own[:, :k] == draft[:, L:]) | done[:, None]
+        n_ok = int(agree.long().cumprod(1).sum(1).min().item())
+    else:
+        n_ok = 0
+    new = own[:, : n_ok + 1]                             # accepted draft tokens (== own) + the target's next token
+    if eos_token_id is not None:
+        for j in range(new.shape[1]):
+            col = torch.where(done, torch.full_like(new[:, j], fill), new[:, j])
+            new[:, j] = col
+            done = done | (col == eos_token_id)
+    return new, done, n_ok
+
+
 def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_ids, max_new_tokens,
                            num_assistant_tokens=5, eos_token_id=None, suppress_tokens=None, min_new_tokens=0,
                            pad_token_id=None, use_cache=True, timestamp_rules=None):
@@ -301,7 +350,15 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
     consumed yet (last accepted + drafts) go through the decoder, against the cached keys/values with the
     bottom-right aligned causal mask -- and rejected positions are dropped by rolling the cache position back; the
     assistant catches up on the accepted tokens the same way and drafts one token per step.  use_cache=False re-decodes
-    the whole prefix every time (cross-check).  Returns (ids [B, P + n], drafted, accepted)."""
+    the whole prefix every time (cross-check).
+
+    Where the engines' ops have `assist_pick` / `assist_accept` (csrc/assist.hip) the cached round runs on device state: one `tokens`
+    buffer [B, total], `done`, `own` and `result` for the whole call; every draft step is the assistant's pass plus one
+    `assist_pick(n=1, store=True)`, the verification the target's pass, one `assist_pick(n=k + 1)` and one `assist_accept`, and the
+    host reads `result` = (accepted drafts, every row done) once per round -- the only synchronisation.  On other ops
+    (oracle.ref_ops, CPU), with DW_ASSIST_TORCH=1, with use_cache=False or beyond `assist_supported` the round is
+    `assist_pick_torch` / `assist_accept_torch`: the same algorithm, the same minimum over the rows.  Equal scores: the lower column
+    wins in the kernels (torch.argmax's order among equals is unspecified on the device).  Returns (ids [B, P + n], drafted, accepted)."""
     dt, da = target.dims, assistant.dims
     B, P0 = prompt_ids.shape
     ids = prompt_ids.clone()
@@ -309,9 +366,14 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
     total = P0 + int(max_new_tokens)
     if total > min(dt.max_tgt, da.max_tgt):
         raise ValueError(f"prompt + max_new_tokens = {total} exceeds max_target_positions")
+    fill = eos_token_id if pad_token_id is None else pad_token_id
+    ops_t, ops_a = target.ops, assistant.ops
+    if (use_cache and all(hasattr(o, "assist_pick") and hasattr(o, "assist_accept") for o in (ops_t, ops_a))
+            and ops_t.assist_supported(B, int(num_assistant_tokens)) and os.environ.get(ASSIST_TORCH_ENV, "0") in ("", "0")):
+        return _assisted_rounds_device(target, assistant, enc_target, enc_assistant, prompt_ids, total, int(num_assistant_tokens),
+                                       eos_token_id, suppress_tokens, int(min_new_tokens), fill, timestamp_rules)
     done = torch.zeros(B, dtype=torch.bool, device=dev)
     drafted = accepted = 0
-    fill = eos_token_id if pad_token_id is None else pad_token_id
     sup = {}
 
     def sup_mask(V):
@@ -324,24 +386,7 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
         return sup[V]
 
     def pick(logits, d, first_pos, hist=None):
-        """greedy tokens from scores [B, n, V] whose row j predicts the token at sequence index first_pos + j (hist: the
-        sequence those positions continue, at least first_pos + n - 1 tokens: history of the timestamp rules)"""
-        sc = logits.float()
-        m = sup_mask(d.vocab)
-        if m is not None:
-            sc = sc + m
-        if eos_token_id is not None and min_new_tokens > 0 and eos_token_id < d.vocab:
-            gen_idx = torch.arange(first_pos - P0, first_pos - P0 + sc.shape[1], device=dev)
-            sc = sc.clone()
-            sc[:, :, eos_token_id] = torch.where((gen_idx < min_new_tokens)[None, :], float("-inf"),
-                                                 sc[:, :, eos_token_id])
-        if timestamp_rules is not None:
-            tr = timestamp_rules
-            sc = torch.stack([apply_timestamp_rules(sc[:, j], hist, first_pos + j, int(tr["begin_index"]),
-                                                    int(tr["no_timestamps_token_id"]), eos_token_id,
-                                                    tr.get("max_initial_timestamp_index"))
-                              for j in range(sc.shape[1])], 1)
-        return sc.argmax(-1)
+        return assist_pick_torch(logits, hist, first_pos, P0, eos_token_id, min_new_tokens, sup_mask(d.vocab), timestamp_rules)
 
     def scores_nocache(eng, d, seq, enc, first):
         T = seq.shape[1]
@@ -376,25 +421,73 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
         else:
             sc = scores_nocache(target, dt, draft, enc_target, L - 1)
         own = pick(sc, dt, L, draft)                         # [B, k + 1]: target's choice after each prefix
-        if k > 0:
-            agree = (own[:, :k] == draft[:, L:]) | done[:, None]
-            n_ok = int(agree.long().cumprod(1).sum(1).min().item())
-        else:
-            n_ok = 0
+        new, done, n_ok = assist_accept_torch(own, draft, L, k, done, eos_token_id, fill)
         drafted += k
         accepted += n_ok
-        new = own[:, : n_ok + 1]                             # accepted draft tokens (== own) + the target's next token
-        if eos_token_id is not None:
-            for j in range(new.shape[1]):
-                col = torch.where(done, torch.full_like(new[:, j], fill), new[:, j])
-                new[:, j] = col
-                done = done | (col == eos_token_id)
         ids = torch.cat([ids, new], 1)
         if use_cache:
             # positions L .. L+n_ok-1 hold accepted drafts (their K/V are valid); everything later is dropped
             ct["t"] = min(ct["t"], L + n_ok)
             ca["t"] = min(ca["t"], L + n_ok)
     return ids, drafted, accepted
+
+
+def _assisted_rounds_device(target, assistant, enc_target, enc_assistant, prompt_ids, total, num_assistant_tokens, eos_token_id,
+                            suppress_tokens, min_new_tokens, fill, timestamp_rules):
+    """The cached rounds of `assisted_greedy_decode` on device state (csrc/assist.hip): the sequence lives in `tokens` [B, total],
+    drafts included; per round k + 2 selection launches, one 8-byte read of `result`."""
+    dt, da = target.dims, assistant.dims
+    ops_t, ops_a = target.ops, assistant.ops
+    B, P0 = prompt_ids.shape
+    dev = prompt_ids.device
+    K = num_assistant_tokens
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    tokens = torch.zeros((B, total), dtype=torch.long, device=dev)
+    tokens[:, :P0].copy_(prompt_ids)
+    cur = torch.zeros((B, 1), dtype=torch.long, device=dev)
+    own = torch.zeros((B, K + 1), dtype=torch.long, device=dev)
+    done = torch.zeros((B,), dtype=torch.bool, device=dev) if eos >= 0 else None
+    result = torch.zeros((2,), dtype=torch.int32, device=dev)
+
+    def mask(V):                                          # decided once, on the host
+        ids = [int(t) for t in (suppress_tokens or []) if 0 <= int(t) < V]
+        if not ids:
+            return None
+        m = torch.zeros((V,), dtype=torch.uint8, device=dev)
+        m[torch.as_tensor(ids, dtype=torch.long, device=dev)] = 1
+        return m
+
+    rk = rule_kwargs(timestamp_rules, eos_token_id)
+    rules = dict(min_new=min_new_tokens if eos >= 0 else 0, ts_begin=rk["ts_begin"], max_initial=rk["max_initial"], begin_index=P0,
+                 eos=eos)
+    sup_t, sup_a = mask(dt.vocab), mask(da.vocab)
+    ct = target.decode_init(enc_target, B, total)
+    ca = assistant.decode_init(enc_assistant, B, total)
+    drafted = accepted = 0
+    L, all_done = P0, False
+    while L < total and not all_done:
+        k = min(K, total - L - 1)
+        for j in range(k):                                   # the assistant drafts k tokens greedily
+            if j == 0:                                       # catch up on what the last round accepted (1 or 2 tokens; the prompt)
+                n = L - ca["t"]
+                logits = assistant.decode_multi(tokens[:, ca["t"]:L], ca)[n - 1:]
+            else:
+                n = 1
+                logits = assistant.decode_step(cur, ca)
+            ops_a.assist_pick(logits, da.vocab, tokens, L + j, own, n=1, batch_rows=n, suppress=sup_a, store=True, cur=cur, **rules)
+        n = L + k - ct["t"]                                  # the target scores what it has not consumed: last accepted + drafts
+        logits = target.decode_multi(tokens[:, ct["t"]:L + k], ct)[n - (k + 1):]
+        ops_t.assist_pick(logits, dt.vocab, tokens, L, own, n=k + 1, batch_rows=n, suppress=sup_t, **rules)
+        ops_t.assist_accept(own, tokens, L, k, result, eos=eos, fill=-1 if fill is None else int(fill), done=done)
+        n_ok, fin = result.tolist()                          # the round's one synchronisation
+        all_done = bool(fin)
+        drafted += k
+        accepted += n_ok
+        # positions L .. L+n_ok-1 hold accepted drafts (their K/V are valid); everything later is dropped
+        ct["t"] = min(ct["t"], L + n_ok)
+        ca["t"] = min(ca["t"], L + n_ok)
+        L += n_ok + 1
+    return tokens[:, :L].clone(), drafted, accepted
 
 
 # DW_BEAM_TORCH=1 (read when a beam search starts): the step stays on the torch ops of `beam_step_torch` on every engine, as on ops

@@ -76,8 +76,12 @@ class ParamStore:
     Frozen tensors come first, trainable ones after, so gradient all-reduce / clip / AdamW see one contiguous range.
     """
 
-    def __init__(self, ops, dims: WhisperDims, state_dict, trainable=False, frozen_prefixes=(), round_bf16=False):
-        self.ops, self.dims, self.trainable = ops, dims, trainable
+    def __init__(self, ops, dims: WhisperDims, state_dict, trainable=False, frozen_prefixes=(), round_bf16=False,
+                 decoder_only=False):
+        """decoder_only: the store holds the `model.decoder.*` entries alone (modeling.WhisperForCausalLM, the assistant of
+        speculative decoding, which drafts on the target's encoder output): no encoder tensor and no packed convolution weight
+        exists on the device, and `WhisperEngine.encode` is not available."""
+        self.ops, self.dims, self.trainable, self.decoder_only = ops, dims, trainable, bool(decoder_only)
         D, Fd = dims.d_model, dims.ffn
         spec = [("model.encoder.conv1.weight", (D, dims.n_mels, 3), "conv"), ("model.encoder.conv1.bias", (D,), "b"),
                 ("model.encoder.conv2.weight", (D, D, 3), "conv"), ("model.encoder.conv2.bias", (D,), "b"),
@@ -96,8 +100,10 @@ class ParamStore:
 
         for i in range(dims.enc_layers):
             spec += [(n, shapes(n, k), k) for n, k in layer_names(f"model.encoder.layers.{i}", False)]
-        spec += [("model.encoder.layer_norm.weight", (D,), "ln"), ("model.encoder.layer_norm.bias", (D,), "ln"),
-                 ("model.decoder.embed_positions.weight", (dims.max_tgt, D), "emb")]
+        spec += [("model.encoder.layer_norm.weight", (D,), "ln"), ("model.encoder.layer_norm.bias", (D,), "ln")]
+        if self.decoder_only:
+            spec = []
+        spec += [("model.decoder.embed_positions.weight", (dims.max_tgt, D), "emb")]
         for i in range(dims.dec_layers):
             spec += [(n, shapes(n, k), k) for n, k in layer_names(f"model.decoder.layers.{i}", True)]
         spec += [("model.decoder.layer_norm.weight", (D,), "ln"), ("model.decoder.layer_norm.bias", (D,), "ln"),
@@ -160,8 +166,10 @@ class ParamStore:
                     rng.append([o, o + _rup(n, 64)])
             self.small_grad_views = [self.G[a:b] for a, b in rng]
         self.kpad1 = _rup(3 * dims.n_mels, 64)
-        self.conv1_packed = ops.zeros((D, self.kpad1), ops.lowp)
-        self.conv2_packed = ops.zeros((D, 3 * D), ops.lowp)
+        self.conv1_packed = self.conv2_packed = None
+        if not self.decoder_only:
+            self.conv1_packed = ops.zeros((D, self.kpad1), ops.lowp)
+            self.conv2_packed = ops.zeros((D, 3 * D), ops.lowp)
         self.load_state_dict(state_dict, round_bf16=round_bf16)
 
     # ------------------------------------------------------------------------------------------------------------
@@ -188,6 +196,8 @@ class ParamStore:
         self.repack_conv()
 
     def repack_conv(self):
+        if self.decoder_only:
+            return
         self.ops.pack_conv_weight(self.p["model.encoder.conv1.weight"], self.kpad1, out=self.conv1_packed)
         self.ops.pack_conv_weight(self.p["model.encoder.conv2.weight"], 3 * self.dims.d_model, out=self.conv2_packed)
 

@@ -539,6 +539,19 @@ def fused_distillation_loss(student_outputs, teacher_outputs, labels, temperatur
     return loss, {"loss": losses[2], "ce_loss": losses[0], "kl_loss": losses[1]}
 
 
+def _assistant_shares_encoder(assistant_model, d):
+    """True: the assistant of speculative decoding drafts on the target's encoder output -- a full model whose owner set
+    `share_encoder_output`, or a decoder-only `WhisperForCausalLM`, which has no encoder of its own (TF hands the target's
+    `encoder_outputs` to such an assistant, TF:generation/candidate_generator.py)."""
+    if getattr(assistant_model, "decoder_only", False):
+        if assistant_model.dims.d_model != d.d_model:
+            raise ValueError(f"the decoder-only assistant has d_model = {assistant_model.dims.d_model}, the model it drafts for "
+                             f"has d_model = {d.d_model}: a WhisperForCausalLM assistant cross-attends to the target's encoder "
+                             "output and needs the same d_model")
+        return True
+    return bool(getattr(assistant_model, "share_encoder_output", None))
+
+
 class WhisperForConditionalGeneration(nn.Module):
     """dtype=torch.float32 (default): fp32 master weights, bf16 GEMM operands, fp32 residual stream -- the reference's
     student under `accelerate` bf16 autocast (SURVEY.md section 8a').  dtype=torch.bfloat16: weights rounded to bf16
@@ -1011,7 +1024,7 @@ class WhisperForConditionalGeneration(nn.Module):
             begin_suppress = None          # TF:719-721: the model must be able to return EOS right away
             assistant_model._sync_shadow()
             ad = assistant_model.dims
-            if getattr(assistant_model, "share_encoder_output", None) or \
+            if _assistant_shares_encoder(assistant_model, d) or \
                     (input_features is None and ad.d_model == d.d_model):
                 enc_a = enc.to(assistant_model.engine.lowp)
             else:
@@ -1479,7 +1492,7 @@ class WhisperForConditionalGeneration(nn.Module):
             if num_beams != 1:
                 raise ValueError("assistant_model cannot be combined with beam search (TF raises the same)")
             am._sync_shadow()
-            shared = bool(getattr(am, "share_encoder_output", None))     # (a distilled student keeps the teacher's encoder)
+            shared = _assistant_shares_encoder(am, d)     # (a distilled student keeps the teacher's encoder)
             a_encode = None if shared else \
                 (lambda f: am.engine.encode(f.to(torch.float32).contiguous(), save=False)[0])
             assistant = (am.engine, a_encode)
@@ -1616,3 +1629,125 @@ class WhisperForConditionalGeneration(nn.Module):
             if eos is not None and bool(done.all()):
                 break
         return ids
+
+
+@dataclass
+class CausalLMOutput:
+    logits: torch.Tensor = None
+
+    def __getitem__(self, i):
+        return (self.logits,)[i]
+
+
+class _DecoderWrapper(nn.Module):                  # TF:modeling_whisper.py `WhisperDecoderWrapper`: the keys are model.decoder.*
+    def __init__(self, d):
+        super().__init__()
+        self.decoder = _Decoder(d)
+
+
+class WhisperForCausalLM(nn.Module):
+    """The decoder-only drop-in of `transformers.WhisperForCausalLM` (TF:modeling_whisper.py): the class the reference loads the
+    distilled student with when it drafts for the teacher (run_eval.py:578-599, README "speculative decoding").  It holds the
+    decoder and the tied LM head and NO encoder parameter -- the flat store is built over the `model.decoder.*` entries
+    (`ParamStore(decoder_only=True)`), so no copy of an encoder exists on the device.  Inference only: `forward(input_ids,
+    encoder_outputs=)` -> `.logits`; as `generate(assistant_model=)` of a `WhisperForConditionalGeneration` it always drafts on
+    that model's encoder output and needs the same d_model.  `generate` on the class itself is not implemented."""
+
+    decoder_only = True
+
+    def __init__(self, config, ops=None, device="cuda:0", state_dict=None, seed=0, dtype=torch.float32):
+        super().__init__()
+        check_regularisers(config)
+        self.config = config
+        self.dims = WhisperDims.from_any(config)
+        self.ops = ops if ops is not None else _default_ops(device)
+        if dtype not in (torch.float32, torch.bfloat16, None):
+            raise ValueError(f"dtype {dtype}: the MI355X path computes in bf16 with fp32 or bf16 parameters")
+        self.dtype_mode = torch.float32 if dtype is None else dtype
+        pure_bf16 = self.dtype_mode == torch.bfloat16
+        if state_dict is None:
+            import dataclasses
+            state_dict = random_state_dict(dataclasses.replace(self.dims, enc_layers=0), seed, device=self.ops.device)
+        sd = {k: v for k, v in state_dict.items() if k.startswith("model.decoder.")}      # a full checkpoint's encoder is ignored
+        if "model.decoder.embed_tokens.weight" not in sd and "proj_out.weight" in state_dict:
+            sd["model.decoder.embed_tokens.weight"] = state_dict["proj_out.weight"]
+        self.store = ParamStore(self.ops, self.dims, sd, trainable=False, round_bf16=pure_bf16, decoder_only=True)
+        self.engine = WhisperEngine(self.ops, self.store, self.ops.lowp if pure_bf16 else torch.float32)
+        self.model = _DecoderWrapper(self.dims)
+        self.proj_out = nn.Linear(self.dims.d_model, self.dims.vocab, bias=False, device="meta")
+        for name in self.store.real_names():
+            mod_path, pname = name.rsplit(".", 1)
+            setattr(self.get_submodule(mod_path), pname, nn.Parameter(self.store.p[name], requires_grad=False))
+        self.proj_out.weight = self.model.decoder.embed_tokens.weight  # tied (TF:modeling_whisper.py `WhisperForCausalLM`)
+        self._param_list = [self.get_parameter(n) for n in self.store.real_names()]
+        self._versions = None
+        from .generation import GenerationConfig
+        self.generation_config = GenerationConfig.from_model_config(config)
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        """Independent tensors under the reference class's keys, the tied `proj_out.weight` one tensor with
+        `model.decoder.embed_tokens.weight` (see WhisperForConditionalGeneration.state_dict)."""
+        sd = nn.Module.state_dict(self, *args, destination=destination, prefix=prefix, keep_vars=keep_vars)
+        if keep_vars:
+            return sd
+        for k in [k for k in sd if k.startswith(prefix)]:
+            sd[k] = sd[k].clone()
+        sd[prefix + "proj_out.weight"] = sd[prefix + "model.decoder.embed_tokens.weight"]
+        return sd
+
+    _sync_shadow = WhisperForConditionalGeneration._sync_shadow
+    save_pretrained = WhisperForConditionalGeneration.save_pretrained
+
+    def get_decoder(self):
+        return self.model.decoder
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, *model_args, config=None, torch_dtype=None, dtype=None, subfolder="",
+                        variant=None, use_safetensors=None, ops=None, device="cuda:0", **kwargs):
+        """Load a LOCAL checkpoint directory: a decoder-only one (`model.decoder.*`, `proj_out.weight`) or a full Whisper
+        checkpoint, of which the decoder tensors are taken and `model.encoder.*` is ignored (as `transformers` loads
+        `distil-whisper/*` checkpoints into this class)."""
+        import os
+        path = os.path.join(str(pretrained_model_name_or_path), subfolder) if subfolder else str(pretrained_model_name_or_path)
+        if not os.path.isdir(path):
+            raise OSError(f"{path} is not a local checkpoint directory (no hub access in this environment)")
+        if config is None:
+            config = WhisperConfig.from_pretrained(path)
+        dt = dtype if dtype is not None else torch_dtype
+        if isinstance(dt, str):
+            dt = {"float32": torch.float32, "bfloat16": torch.bfloat16, "auto": None}.get(dt, dt)
+        st_path = os.path.join(path, "model.safetensors" if not variant else f"model.{variant}.safetensors")
+        bin_path = os.path.join(path, "pytorch_model.bin")
+        if os.path.exists(st_path) and use_safetensors is not False:
+            from safetensors import safe_open
+            with safe_open(st_path, framework="pt") as f:                  # (the encoder tensors of a full checkpoint are not read)
+                sd = {k: f.get_tensor(k) for k in f.keys() if not k.startswith("model.encoder.")}
+        elif os.path.exists(bin_path):
+            sd = torch.load(bin_path, map_location="cpu", weights_only=True)
+        else:
+            raise OSError(f"no model.safetensors / pytorch_model.bin under {path}")
+        return cls(config, ops=ops, device=device, state_dict=sd, dtype=dt)
+
+    @torch.no_grad()
+    def forward(self, input_ids=None, attention_mask=None, encoder_outputs=None, **kwargs):
+        """Logits [B, T, V] of the teacher-forced decoder pass over `input_ids` against `encoder_outputs` (a tensor [B, Lk, D],
+        a tuple or an output object whose first entry is one).  Inference only: no `labels`, nothing is kept for a backward."""
+        d = self.dims
+        if kwargs.get("labels") is not None:
+            raise NotImplementedError("WhisperForCausalLM is inference-only on the MI355X path (no labels / loss)")
+        if input_ids is None or encoder_outputs is None:
+            raise ValueError("input_ids and encoder_outputs are required (this class has no encoder)")
+        enc = encoder_outputs
+        if not torch.is_tensor(enc):
+            enc = enc.last_hidden_state if hasattr(enc, "last_hidden_state") else enc[0]
+        B, T = input_ids.shape
+        if enc.numel() != B * d.max_src * d.d_model:
+            raise ValueError(f"encoder_outputs must cover {d.max_src} positions of width {d.d_model} per row")
+        self._sync_shadow()
+        enc = enc.reshape(-1, d.d_model).to(self.engine.lowp).contiguous()
+        logits, _ = self.engine.decode(input_ids.contiguous(), enc, save=False)
+        return CausalLMOutput(logits=logits[: B * T, : d.vocab].float().view(B, T, d.vocab))
+
+    def generate(self, *args, **kwargs):
+        raise NotImplementedError("WhisperForCausalLM drafts for a WhisperForConditionalGeneration (`generate(assistant_model=)`); "
+                                  "`generate` on the decoder-only class itself is not implemented on the MI355X path")

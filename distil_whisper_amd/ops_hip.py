@@ -110,6 +110,10 @@ _SIGS = {
                             C.c_void_p, C.c_void_p], C.c_int),
     "dw_beam_update": ([C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_float] * 2 + [C.c_void_p] * 4 + [C.c_int64] +
                        [C.c_void_p] * 10, C.c_int),
+    "dw_assist_pick": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                        C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "dw_assist_accept": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                          C.c_void_p, C.c_void_p], C.c_int),
     "dw_cross_attn_probs": ([C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int64,
                                                                                                     C.c_float, C.c_void_p], C.c_int),
     "dw_align_prepare": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -730,6 +734,44 @@ class HipOps:
             float(fin_div), float(hyp_div), _p(running_in), _p(running_out), _p(sequences_in), _p(sequences_out),
             running_in.shape[2], _p(run_scores), _p(beam_scores), _p(finished), _p(lengths), _p(unsat), _p(stop), _p(src_rows),
             _p(next_tok), _p(plan), self._stream()), "beam_update")
+
+    # ---- speculative decoding (csrc/assist.hip; TF:generation/utils.py `_assisted_decoding`) ---------------------------------------
+    ASSIST_MAX_BATCH, ASSIST_MAX_DRAFTS = 1024, 1024
+
+    def assist_supported(self, B, k):
+        """False: dw_assist_accept would answer DW_EUNSUP (the caller keeps its torch step)."""
+        return 1 <= int(B) <= self.ASSIST_MAX_BATCH and 0 <= int(k) <= self.ASSIST_MAX_DRAFTS
+
+    def assist_pick(self, logits, V, tokens, L, own, *, n=1, batch_rows=None, suppress=None, begin_suppress=None, min_new=0,
+                    ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, store=False, cur=None):
+        """The tokens the rules of `greedy_select` pick at the n positions L .. L + n - 1 of every row, no EOS bookkeeping: logits
+        bf16 [>= (B - 1) * batch_rows + n, ld], row b * batch_rows + j predicts tokens[b, L + j] from the history tokens[b, :L + j]
+        (batch_rows defaults to n); tokens int64 [B, >= L + n - 1]; own int64 [B, >= n] receives them.  store (n == 1): the token
+        goes to tokens[:, L] and cur (int64 [B, 1]) as well -- the assistant's draft step."""
+        B, n = tokens.shape[0], int(n)
+        rows = n if batch_rows is None else int(batch_rows)
+        self._check_select(logits, (B - 1) * rows + n, V, suppress, begin_suppress)
+        assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[1] >= L + n - (0 if store else 1)
+        assert own.dtype == torch.int64 and own.stride(1) == 1 and own.shape[0] >= B and own.shape[1] >= n
+        assert rows >= n >= 1 and logits.shape[1] >= V and 1 <= begin_index <= L
+        if store:
+            assert n == 1 and cur is not None and cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() >= B
+        self._chk(self.lib.dw_assist_pick(
+            _p(logits), B, n, int(V), logits.stride(0), rows, _p(suppress), _p(begin_suppress), int(min_new), int(ts_begin),
+            int(max_initial), _p(tokens), tokens.stride(0), int(L), int(begin_index), int(eos), _p(own), own.stride(0), int(store),
+            _p(cur) if store else None, self._stream()), "assist_pick")
+
+    def assist_accept(self, own, tokens, L, k, result, *, eos=-1, fill=-1, done=None):
+        """The bookkeeping of one round (include/dwamd.h dw_assist_accept): own int64 [B, >= k + 1] from `assist_pick(n=k + 1)`,
+        the k drafts at tokens[:, L:L + k]; writes tokens[:, L:L + n_ok + 1], done bool [B] in/out and result int32 [2] = (n_ok,
+        every row done)."""
+        B = tokens.shape[0]
+        assert own.dtype == torch.int64 and own.stride(1) == 1 and own.shape[0] >= B and own.shape[1] >= k + 1
+        assert tokens.dtype == torch.int64 and tokens.stride(1) == 1 and tokens.shape[1] >= L + k + 1 and L >= 1 and k >= 0
+        assert result.dtype == torch.int32 and result.is_contiguous() and result.numel() >= 2
+        assert (done is None and eos < 0) or (done.dtype == torch.bool and done.is_contiguous() and done.numel() >= B)
+        self._chk(self.lib.dw_assist_accept(_p(own), own.stride(0), _p(tokens), tokens.stride(0), B, int(L), int(k), int(eos),
+                                            int(fill), _p(done), _p(result), self._stream()), "assist_accept")
 
     # ---- token-level timestamps (csrc/align.hip; TF:generation_whisper.py:241-381) ------------------------------------
     def cross_attn_probs(self, q, k, heads, probs, slot0, B, L, Lk, kv_batch_rows=None, scale=0.125):

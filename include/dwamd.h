@@ -337,6 +337,28 @@ int dw_beam_update(const float* cand_val, const int32_t* cand_tok, int B, int k,
                    uint8_t* finished, int32_t* lengths, uint8_t* unsat, int32_t* stop, int64_t* src_rows, int64_t* next_tok,
                    int32_t* plan, void* stream);
 
+/* ---- speculative (assisted) greedy decoding: the selection and the bookkeeping of one round (TF:generation/utils.py
+ * `_assisted_decoding`, greedy; reached from run_eval.py:578-599, 706-707 `assistant_model=`; csrc/assist.hip).
+ * dw_assist_pick: the token the rules of dw_greedy_select pick at n consecutive positions of every row, without the EOS / pad
+ * bookkeeping.  logits bf16, V valid columns (ld >= V, a multiple of 4; base 8-byte aligned): the row at element offset
+ * (b * batch_rows + j) * ld predicts tokens[b][L + j], j < n (batch_rows >= n).  tokens int64 [B][tok_ld]: position (b, j) is
+ * judged against the history tokens[b][0, L + j) -- for j > 0 it includes the drafts at [L, L + j), which must be in place --
+ * with begin_index = the decoder prompt length (1 <= begin_index <= L), begin_suppress at L + j == begin_index only, eos masked
+ * while L + j - begin_index < min_new, ts_begin / max_initial / suppress as in dw_greedy_select, the timestamp mass rule
+ * included; among equal scores the lower column wins.  own int64 [B][own_ld] (own_ld >= n) receives the tokens.  store != 0
+ * (n == 1 only; the assistant's draft step): the token also goes to tokens[b][L] and cur[b] (int64 [B]).  No `done`: a draft
+ * continues past an EOS it drafted.  One workgroup per (j, b); any V that dw_greedy_select takes; B <= 65535. */
+int dw_assist_pick(const void* logits, int B, int n, int V, int64_t ld, int64_t batch_rows, const uint8_t* suppress,
+                   const uint8_t* begin_suppress, int min_new, int ts_begin, int max_initial, int64_t* tokens, int64_t tok_ld,
+                   int L, int begin_index, int eos, int64_t* own, int64_t own_ld, int store, int64_t* cur, void* stream);
+/* dw_assist_accept: with own [B][own_ld] from dw_assist_pick(n = k + 1) and the k drafts at tokens[b][L, L + k): m_b = the number
+ * of leading j < k with own[b][j] == tokens[b][L + j] (k for a row whose done[b] is set), n_ok = min over b (0 when k == 0); then
+ * for j = 0 .. n_ok in order: c = done[b] ? fill : own[b][j]; tokens[b][L + j] = c; done[b] |= (c == eos).  eos < 0: no `done`
+ * handling (done may be NULL).  result int32 [2] = {n_ok, eos >= 0 and every row done}.  Positions behind L + n_ok keep what
+ * they hold.  One workgroup, one thread per row: B <= 1024 and k <= 1024, else DW_EUNSUP (the caller keeps its torch step). */
+int dw_assist_accept(const int64_t* own, int64_t own_ld, int64_t* tokens, int64_t tok_ld, int B, int L, int k, int eos, int fill,
+                     uint8_t* done, int32_t* result, void* stream);
+
 /* ---- a11: one decoder pass of cached greedy decoding as ONE call (the `decode_step` entry of SURVEY.md 8b).
  * Replaces `WhisperDecoder.forward` + `proj_out` on the cache branch (TF:modeling_whisper.py:690-795, 312-335, 1080)
  * as reached from `generate` (run_eval.py:739, run_distillation.py:1524-1528, run_pseudo_labelling.py:861-996).
