@@ -7,20 +7,19 @@
 // matching drafts plus the target's own next token; reached from run_eval.py:578-599, 706-707 (`assistant_model=`).  What the
 // host loop of decoding.assisted_greedy_decode did with a dozen torch ops and two synchronisations per round:
 //
-//   dw_assist_pick    the token the logits rules select at n consecutive positions of every row -- greedy_select_kernel<false>
-//                     (decode.hip) without its EOS bookkeeping and over a (position, row) grid like score_tokens_kernel
-//                     (score.hip).  Position j of row b is judged against the history tokens[b][0, L + j): for j > 0 that
-//                     history holds the drafts, which the draft steps stored before this launch, so the n positions of a row are
-//                     independent workgroups.  The rules are those of select_rules.h (row_rules, rule_masks_of, classify_chunk,
-//                     column_allowed); this file holds none of its own.
+//   dw_assist_pick    the token the logits rules select at n consecutive positions of every row: the greedy walk of
+//                     select_rules.h (greedy_pick, shared with decode.hip) over a (position, row) grid like score_tokens_kernel
+//                     (score.hip), with no EOS bookkeeping.  Position j of row b is judged against the history
+//                     tokens[b][0, L + j): for j > 0 that history holds the drafts, which the draft steps stored before this
+//                     launch, so the n positions of a row are independent workgroups.  This file holds no rule and no walk of
+//                     its own: which row and position, and where the token is written.
 //   dw_assist_accept  the round's bookkeeping for the whole batch in one workgroup, one thread per row: the length of the
 //                     agreeing draft prefix, its minimum over the rows, the accepted tokens with the finished rows filled.
 //
 // Both are plain kernels on the caller's stream: nothing is allocated, nothing synchronises, no workgroup waits for another.
-// Cost model of the pick: as greedy_select_kernel, a row lives on one CU and is bound by instructions per column (13 chunks of
-// four columns per thread at V = 51 866, all requested before any is judged); n x B rows run side by side on the 256 CUs.
+// Cost model of the pick: that of greedy_pick (a row lives on one CU); n x B rows run side by side on the 256 CUs.
 #include "common.h"
-#include "select_rules.h"                           // SEL_NT, Best / block_best and every logits rule
+#include "select_rules.h"                           // SEL_NT, Best, every logits rule and the greedy walk
 #include "../../include/dwamd.h"
 
 struct AssistPickP {
@@ -42,75 +41,8 @@ __global__ __launch_bounds__(SEL_NT) void assist_pick_kernel(const AssistPickP p
     const int n = p.L + j;                          // the sequence index this workgroup fills
     const bf16* row = p.logits + ((long)b * p.batch_rows + j) * p.ld;
     const int first = n == p.P0;
-    const uint8_t* suppress = p.suppress;
-    const uint8_t* begin_suppress = first ? p.begin_suppress : nullptr;      // (so that word_masks asks nothing of an unused mask)
     const RowRules rr = row_rules(row_tok, n, p.P0, p.tb, p.max_initial, V, p.eos, (n - p.P0) < p.min_new, redi);
-    const int tsb = rr.tsb;
-    const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
-    auto masks_of = [&](int c0) -> unsigned { return rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V); };
-    // ---- pass 1: best allowed text token and best allowed timestamp token (the chunk walk of greedy_select_kernel) ----
-    Best bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
-    auto judge = [&](int c0, const bf16x4& x, unsigned mask, bool live) {
-        const ChunkKind kind = classify_chunk(rr, mask, live, c0, V);
-        if (kind.clean) {                              // ascending order within a thread: the strict compare keeps the first of equals
-            const bool in_text = kind.in_text;
-            float bv = in_text ? bt.v : bs.v;
-            int bi = in_text ? bt.i : bs.i;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float v = bf2f(x[e]);
-                if (v > bv) { bv = v; bi = c0 + e; }
-            }
-            if (in_text) { bt.v = bv; bt.i = bi; } else { bs.v = bv; bs.i = bi; }
-            return;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int c = c0 + e;
-            if (column_allowed(rr, c0, e, V, mask, 0u, live)) {
-                const Best cand = {bf2f(x[e]), c};
-                if (c < tsb) bt = better(bt, cand); else bs = better(bs, cand);
-            }
-        }
-    };
-    constexpr int NPRE = 13;                           // 13 x 4096 columns cover every Whisper vocabulary (51 866)
-    if (V <= NPRE * SEL_NT * 4) {
-        // the whole row is requested before anything is judged, with clamped addresses instead of branches around the loads
-        const int clast = (V - 1) & ~3;
-        bf16x4 xr[NPRE];
-        unsigned mr[NPRE];
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) {
-            const int c0 = min(tid * 4 + i * SEL_NT * 4, clast);
-            xr[i] = *(const bf16x4*)(row + c0);
-            mr[i] = masks_of(c0);
-        }
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) {
-            const int c0 = tid * 4 + i * SEL_NT * 4;
-            judge(min(c0, clast), xr[i], mr[i], c0 < V);
-        }
-    } else {
-        for (int c0 = tid * 4; c0 < V; c0 += SEL_NT * 4) judge(c0, *(const bf16x4*)(row + c0), masks_of(c0), true);
-    }
-    bt = block_best(bt, red);
-    bs = block_best(bs, red);
-    Best pick = better(bt, bs);
-    if (rr.ts_mode && bs.v > -INFINITY) {
-        // mass rule: if logsumexp over the allowed timestamps exceeds the best text logit, a timestamp is taken
-        float sum = 0.f;
-        for (int c = tsb + tid; c < V; c += SEL_NT) {
-            const unsigned masked = (suppress && suppress[c]) || (begin_suppress && begin_suppress[c]);
-            if (column_allowed(rr, c, 0, V, masked)) sum += __expf(bf2f(row[c]) - bs.v);
-        }
-        sum = wave_sum(sum);
-        __syncthreads();
-        if ((tid & 63) == 0) redf[tid >> 6] = sum;
-        __syncthreads();
-        sum = 0.f;
-        for (int i = 0; i < SEL_NT / 64; ++i) sum += redf[i];
-        if (bs.v + __logf(sum) > bt.v) pick = bs;
-    }
+    const Best pick = greedy_pick<false>(row, V, p.suppress, p.begin_suppress, first, rr, nullptr, nullptr, 1.0f, red, redf);
     if (tid == 0) {
         const long nxt = pick.i == 0x7fffffff ? 0 : pick.i;
         p.own[(long)b * p.own_ld + j] = nxt;

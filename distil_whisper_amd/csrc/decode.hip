@@ -17,7 +17,7 @@
 // TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper (TF:logits_process.py, in TF:utils.py `_get_logits_processor`'s
 // order), `softmax` + `torch.multinomial` of TF:utils.py `_sample`, as reached from run_eval.py:690-739 (temperature fallback).
 #include "common.h"
-#include "select_rules.h"                           // SEL_NT, Best / block_best and every logits rule
+#include "select_rules.h"                           // SEL_NT, Best / block_best, every logits rule and the greedy walk
 #include "../../include/dwamd.h"
 
 // dw_debug_set key 7 (A/B): bit 0 LayerNorm-on-load off, bit 1 K/V append fusion off, bit 2 / bit 3: the self- / cross-attention of
@@ -35,7 +35,7 @@ int g_decode_fuse_off = 4;
 // NoRepeatNGramLogitsProcessor -- a column that would complete an n-gram the row already holds is excluded.  Both are
 // predicates on (column, row history) like the rest: the workgroup turns the <= 448 history tokens into two bitmaps in LDS
 // (one bit per column: `seen`, `banned`, select_rules.h); a four-column chunk whose bits are all clear keeps the short path of
-// `judge`.
+// the walk (greedy_pick, select_rules.h), which both instances share with assist_pick_kernel (assist.hip).
 template <bool HIST>
 __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     const bf16* logits, int V, long ld, const uint8_t* suppress, const uint8_t* begin_suppress, int first, int no_eos,
@@ -53,92 +53,8 @@ __global__ __launch_bounds__(SEL_NT) void greedy_select_kernel(
     }
     const bf16* row = logits + (long)b * ld;
     if constexpr (HIST) build_history_bitmaps(row_tok, n, V, rep_pen, ngram, seen, banned);
-    auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
     const RowRules rr = row_rules(row_tok, n, begin_index, tb, max_initial, V, eos, no_eos, redi);
-    const int tsb = rr.tsb;
-    auto allowed = [&](int c) -> bool {               // (used by the probability-mass pass below)
-        const unsigned masked = (suppress && suppress[c]) || (first && begin_suppress && begin_suppress[c]);
-        unsigned ban = 0;
-        if constexpr (HIST) ban = banned[c >> 5] >> (c & 31);
-        return column_allowed(rr, c, 0, V, masked, ban);
-    };
-    // ---- pass 1: best allowed text token and best allowed timestamp token ----
-    // (the byte masks are fetched four columns at a time; the next chunk is requested before the current one is judged)
-    const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
-    Best bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
-    auto masks_of = [&](int c0) -> unsigned { return rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V); };
-    // A row lives on ONE CU (one workgroup), so the kernel is bound by instructions per column, not by bytes: a chunk of
-    // four columns that lies inside one allowed interval with no mask bit and no banned id (almost every chunk) takes
-    // the short path -- a compare and two selects per column; ascending order within a thread makes the strict compare
-    // keep the smallest index among equal values.
-    auto judge = [&](int c0, const bf16x4& x, unsigned mask, bool live) {
-        unsigned sbits = 0, bbits = 0;                 // bit e: column c0 + e is in the history / banned
-        if constexpr (HIST) { sbits = history_bits_of(seen, c0); bbits = history_bits_of(banned, c0); }
-        const ChunkKind kind = classify_chunk(rr, mask, live, c0, V, sbits, bbits);
-        if (kind.clean) {
-            const bool in_text = kind.in_text;
-            float bv = in_text ? bt.v : bs.v;
-            int bi = in_text ? bt.i : bs.i;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float v = bf2f(x[e]);
-                if (v > bv) { bv = v; bi = c0 + e; }
-            }
-            if (in_text) { bt.v = bv; bt.i = bi; } else { bs.v = bv; bs.i = bi; }
-            return;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int c = c0 + e;
-            if (column_allowed(rr, c0, e, V, mask, bbits, live)) {
-                float v = bf2f(x[e]);
-                if constexpr (HIST) { if ((sbits >> e) & 1u) v = penal(v); }
-                const Best cand = {v, c};
-                if (c < tsb) bt = better(bt, cand); else bs = better(bs, cand);
-            }
-        }
-    };
-    constexpr int NPRE = 13;                           // 13 x 4096 columns cover every Whisper vocabulary (51 866)
-    if (V <= NPRE * SEL_NT * 4) {
-        // The whole row is requested before anything is judged, with clamped addresses instead of branches around the
-        // loads: as a loop, a thread's 13 chunks were 13 dependent L2 round trips (10 of the kernel's 19 us).
-        const int clast = (V - 1) & ~3;
-        bf16x4 xr[NPRE];
-        unsigned mr[NPRE];
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) {
-            const int c0 = min(tid * 4 + i * SEL_NT * 4, clast);
-            xr[i] = *(const bf16x4*)(row + c0);
-            mr[i] = masks_of(c0);
-        }
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) {
-            const int c0 = tid * 4 + i * SEL_NT * 4;
-            judge(min(c0, clast), xr[i], mr[i], c0 < V);
-        }
-    } else {
-        for (int c0 = tid * 4; c0 < V; c0 += SEL_NT * 4) judge(c0, *(const bf16x4*)(row + c0), masks_of(c0), true);
-    }
-    bt = block_best(bt, red);
-    bs = block_best(bs, red);
-    Best pick = better(bt, bs);
-    if (rr.ts_mode && bs.v > -INFINITY) {
-        // sampled mass rule: if logsumexp over the allowed timestamps exceeds the best text logit, a timestamp is taken
-        float sum = 0.f;
-        for (int c = tsb + tid; c < V; c += SEL_NT)
-            if (allowed(c)) {
-                float v = bf2f(row[c]);
-                if constexpr (HIST) { if ((seen[c >> 5] >> (c & 31)) & 1u) v = penal(v); }
-                sum += __expf(v - bs.v);
-            }
-        sum = wave_sum(sum);
-        __syncthreads();
-        if ((tid & 63) == 0) redf[tid >> 6] = sum;
-        __syncthreads();
-        sum = 0.f;
-        for (int i = 0; i < SEL_NT / 64; ++i) sum += redf[i];
-        if (bs.v + __logf(sum) > bt.v) pick = bs;
-    }
+    const Best pick = greedy_pick<HIST>(row, V, suppress, begin_suppress, first, rr, seen, banned, rep_pen, red, redf);
     if (tid == 0) {
         long nxt = pick.i == 0x7fffffff ? 0 : pick.i;
         if (eos >= 0) {

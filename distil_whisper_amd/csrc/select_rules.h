@@ -1,10 +1,12 @@
 // The one statement of the reference's logits rules (MinNewTokensLength, SuppressTokens, SuppressTokensAtBegin and
 // WhisperTimeStampLogitsProcessor, TF:generation/logits_process.py; RepetitionPenalty / NoRepeatNGram as history bitmaps) for the
 // kernels that apply them -- decode.hip: greedy / history / sampled selection; beam.hip: beam-search candidates; score.hip: scores
-// of finished sequences -- with the workgroup shape and the (value, index) reduction they share.  A rule changes here and
-// nowhere else: the row state as two allowed id intervals plus two single banned ids (row_rules), the byte masks
+// of finished sequences; assist.hip: the picks of a speculative round -- with the workgroup shape and the (value, index) reduction
+// they share.  A rule changes here and nowhere else: the row state as two allowed id intervals plus two single banned ids (row_rules), the byte masks
 // (rule_masks_of), the history bitmaps (build_history_bitmaps), the clean-chunk test (classify_chunk) and the per-column
-// predicate (column_allowed).  What the kernels keep to themselves is arithmetic: how they hold a row and in which order they sum.
+// predicate (column_allowed).  What the kernels keep to themselves is arithmetic: how they hold a row and in which order they sum
+// -- except the kernels that keep only a row's argmax (greedy_select_kernel<false / true>, assist.hip's assist_pick_kernel): their
+// walk over the row is greedy_pick below, once.
 #pragma once
 #include "common.h"
 
@@ -154,6 +156,106 @@ __device__ __forceinline__ bool column_allowed(const RowRules& r, int c0, int e,
     const int c = c0 + e;
     return live && c < V && !((mask >> (8 * e)) & 0xffu) && ((c >= r.tlo && c < r.thi) || (c >= r.slo && c < r.shi)) &&
            c != r.ban_eos && c != r.ban_nots && !((bbits >> e) & 1u);
+}
+
+// The greedy walk: the row's best allowed column under every rule above -- Best{value, column}, column 0x7fffffff when no column
+// is allowed -- for the kernels that keep nothing of a row but its argmax (decode.hip greedy_select_kernel<HIST>, assist.hip
+// assist_pick_kernel).  Called by all SEL_NT threads.  row: V bf16 logits, 8-byte aligned; begin_suppress counts only when
+// `first` (tested at each use: with the pointer nulled instead greedy_select_kernel<true> ran 0.15 us slower,
+// profiles/greedy_walk_refactor.md); HIST: seen / banned are the complete bitmaps of build_history_bitmaps and a seen column
+// takes RepetitionPenaltyLogitsProcessor's v < 0 ? v * rep_pen : v / rep_pen (all three unused without HIST); red / redf:
+// SEL_NT / 64 entries of LDS each.
+// Pass 1 keeps the best allowed text token and the best allowed timestamp token, pass 2 (timestamp rules only) sums the
+// timestamp probability mass for the "timestamps together beat the best text token" rule.  A row lives on ONE CU (one
+// workgroup), so the walk is bound by instructions per column, not by bytes: a chunk of four columns that classify_chunk calls
+// clean (almost every chunk) takes the short path of `judge` -- a compare and two selects per column; ascending order within a
+// thread makes the strict compare keep the smallest index among equal values, better() does the same everywhere else.
+template <bool HIST>
+__device__ __forceinline__ Best greedy_pick(const bf16* row, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
+                                            const RowRules& rr, const unsigned* seen, const unsigned* banned, float rep_pen,
+                                            Best* red, float* redf) {
+    const int tid = threadIdx.x;
+    const int tsb = rr.tsb;
+    auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
+    auto allowed = [&](int c) -> bool {               // (one column on its own: the probability-mass pass below)
+        const unsigned masked = (suppress && suppress[c]) || (first && begin_suppress && begin_suppress[c]);
+        unsigned ban = 0;
+        if constexpr (HIST) ban = banned[c >> 5] >> (c & 31);
+        return column_allowed(rr, c, 0, V, masked, ban);
+    };
+    // ---- pass 1: best allowed text token and best allowed timestamp token (the byte masks four columns at a time) ----
+    const bool word_masks = (((uintptr_t)suppress | (uintptr_t)begin_suppress) & 3) == 0;
+    auto masks_of = [&](int c0) -> unsigned { return rule_masks_of(suppress, begin_suppress, first, word_masks, c0, V); };
+    Best bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
+    auto judge = [&](int c0, const bf16x4& x, unsigned mask, bool live) {
+        unsigned sbits = 0, bbits = 0;                 // bit e: column c0 + e is in the history / banned
+        if constexpr (HIST) { sbits = history_bits_of(seen, c0); bbits = history_bits_of(banned, c0); }
+        const ChunkKind kind = classify_chunk(rr, mask, live, c0, V, sbits, bbits);
+        if (kind.clean) {
+            const bool in_text = kind.in_text;
+            float bv = in_text ? bt.v : bs.v;
+            int bi = in_text ? bt.i : bs.i;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float v = bf2f(x[e]);
+                if (v > bv) { bv = v; bi = c0 + e; }
+            }
+            if (in_text) { bt.v = bv; bt.i = bi; } else { bs.v = bv; bs.i = bi; }
+            return;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = c0 + e;
+            if (column_allowed(rr, c0, e, V, mask, bbits, live)) {
+                float v = bf2f(x[e]);
+                if constexpr (HIST) { if ((sbits >> e) & 1u) v = penal(v); }
+                const Best cand = {v, c};
+                if (c < tsb) bt = better(bt, cand); else bs = better(bs, cand);
+            }
+        }
+    };
+    constexpr int NPRE = 13;                           // 13 x 4096 columns cover every Whisper vocabulary (51 866)
+    if (V <= NPRE * SEL_NT * 4) {
+        // The whole row is requested before anything is judged, with clamped addresses instead of branches around the
+        // loads: as a loop, a thread's 13 chunks were 13 dependent L2 round trips (10 of the kernel's 19 us).
+        const int clast = (V - 1) & ~3;
+        bf16x4 xr[NPRE];
+        unsigned mr[NPRE];
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) {
+            const int c0 = min(tid * 4 + i * SEL_NT * 4, clast);
+            xr[i] = *(const bf16x4*)(row + c0);
+            mr[i] = masks_of(c0);
+        }
+#pragma unroll
+        for (int i = 0; i < NPRE; ++i) {
+            const int c0 = tid * 4 + i * SEL_NT * 4;
+            judge(min(c0, clast), xr[i], mr[i], c0 < V);
+        }
+    } else {
+        for (int c0 = tid * 4; c0 < V; c0 += SEL_NT * 4) judge(c0, *(const bf16x4*)(row + c0), masks_of(c0), true);
+    }
+    bt = block_best(bt, red);
+    bs = block_best(bs, red);
+    Best pick = better(bt, bs);
+    if (rr.ts_mode && bs.v > -INFINITY) {
+        // mass rule: if logsumexp over the allowed timestamps exceeds the best text logit, a timestamp is taken
+        float sum = 0.f;
+        for (int c = tsb + tid; c < V; c += SEL_NT)
+            if (allowed(c)) {
+                float v = bf2f(row[c]);
+                if constexpr (HIST) { if ((seen[c >> 5] >> (c & 31)) & 1u) v = penal(v); }
+                sum += __expf(v - bs.v);
+            }
+        sum = wave_sum(sum);
+        __syncthreads();
+        if ((tid & 63) == 0) redf[tid >> 6] = sum;
+        __syncthreads();
+        sum = 0.f;
+        for (int i = 0; i < SEL_NT / 64; ++i) sum += redf[i];
+        if (bs.v + __logf(sum) > bt.v) pick = bs;
+    }
+    return pick;
 }
 
 // Host side, for the C entries of these kernels (the one header they share): what every entry asks of the logits rows and of

@@ -112,8 +112,49 @@ def rule_kwargs(timestamp_rules, eos):
     GreedyDecoder, or None) and the EOS id (None: no EOS bookkeeping)."""
     r = timestamp_rules
     mi = None if r is None else r.get("max_initial_timestamp_index")
-    return dict(ts_begin=-1 if r is None else r["no_timestamps_token_id"] + 1, max_initial=-1 if mi is None else mi,
-                begin_index=1 if r is None else r["begin_index"], eos=-1 if eos is None else eos)
+    return dict(ts_begin=-1 if r is None else int(r["no_timestamps_token_id"]) + 1, max_initial=-1 if mi is None else int(mi),
+                begin_index=1 if r is None else int(r.get("begin_index", 1)), eos=-1 if eos is None else int(eos))
+
+
+def token_mask(ids, V, device, dtype=torch.bool):
+    """Token ids as a mask over the vocabulary: `dtype` [V], 1 at every id that lies in [0, V); None when none does.  An id beyond
+    the vocabulary names no column and is dropped, as by the reference's `torch.isin(arange(V), ids)` (SuppressTokensLogitsProcessor)."""
+    ids = sorted({int(t) for t in ([] if ids is None else ids) if 0 <= int(t) < V})
+    if not ids:
+        return None
+    m = torch.zeros((V,), dtype=dtype, device=device)
+    m[torch.as_tensor(ids, dtype=torch.long, device=device)] = 1
+    return m
+
+
+def processed_scores(scores, hist, n, *, begin_index, eos=None, no_eos=False, first=False, suppress=None, begin_suppress=None,
+                     timestamp_rules=None, repetition_penalty=None, no_repeat_ngram=0):
+    """The scores of one step after the reference's logits processors, in its order (TF `_get_logits_processor`, then
+    TF:generation_whisper.py:1774-1812): RepetitionPenalty, NoRepeatNGram, MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens,
+    WhisperTimeStamp -> f32 [rows, V].  This is the one torch statement of what the selection kernels judge (csrc/select_rules.h):
+    every torch path of the package and oracle.ref_ops select from it.  scores [rows, V] (logits, or their log-softmax under beam
+    search; left unchanged); hist int64 [rows, >= n] of which the first n are the sequence so far, decoder prompt of `begin_index`
+    tokens included; no_eos: fewer than min_new_tokens generated, EOS (`eos`, None: there is none) is excluded; first: position n
+    is the first generated one, where `begin_suppress` counts; suppress / begin_suppress: bool or uint8 [>= V], non-zero = excluded
+    (`token_mask`), or None; timestamp_rules: None or dict(no_timestamps_token_id, max_initial_timestamp_index)."""
+    neg = float("-inf")
+    V = scores.shape[-1]
+    sc = scores.float()
+    if repetition_penalty is not None and float(repetition_penalty) != 1.0:
+        sc = apply_repetition_penalty(sc, hist[:, :n], float(repetition_penalty))
+    if no_repeat_ngram:
+        sc = apply_no_repeat_ngram(sc, hist[:, :n], int(no_repeat_ngram))
+    if no_eos and eos is not None and 0 <= eos < V:
+        sc = sc.clone()
+        sc[:, eos] = neg
+    if first and begin_suppress is not None:
+        sc = sc.masked_fill(begin_suppress[:V].bool()[None, :], neg)
+    if suppress is not None:
+        sc = sc.masked_fill(suppress[:V].bool()[None, :], neg)
+    if timestamp_rules is not None:
+        sc = apply_timestamp_rules(sc, hist, n, int(begin_index), int(timestamp_rules["no_timestamps_token_id"]), eos,
+                                   timestamp_rules.get("max_initial_timestamp_index"))
+    return sc
 
 
 class GreedyDecoder:
@@ -132,14 +173,8 @@ class GreedyDecoder:
         self.cur = torch.zeros((self.B, 1), dtype=torch.long, device=dev)
         self.done = torch.zeros((self.B,), dtype=torch.bool, device=dev)
 
-        def mask(ids):
-            if ids is None or len(ids) == 0:
-                return None
-            m = torch.zeros((d.vocab,), dtype=torch.uint8, device=dev)
-            m[torch.as_tensor(list(ids), dtype=torch.long, device=dev)] = 1
-            return m
-        self.suppress = mask(suppress_tokens)
-        self.begin_suppress = mask(begin_suppress_tokens)
+        self.suppress = token_mask(suppress_tokens, d.vocab, dev, torch.uint8)
+        self.begin_suppress = token_mask(begin_suppress_tokens, d.vocab, dev, torch.uint8)
         # dict(begin_index=, no_timestamps_token_id=, max_initial_timestamp_index=): WhisperTimeStampLogitsProcessor
         self.timestamp_rules = timestamp_rules
         if timestamp_rules is not None and eos_token_id is None:
@@ -206,23 +241,10 @@ class GreedyDecoder:
         """Token n of every row from `logits` with the history-dependent processors / sampling of `self.soft`."""
         d, so, r = self.eng.dims, self.soft, self.timestamp_rules
         B = self.B
-        neg = float("-inf")
-        sc = logits[:B, :d.vocab].float()
-        hist = self.tokens[:, :n]
-        rp = so.get("repetition_penalty")
-        if rp is not None and float(rp) != 1.0:
-            sc = apply_repetition_penalty(sc, hist, float(rp))
-        if so.get("no_repeat_ngram_size"):
-            sc = apply_no_repeat_ngram(sc, hist, int(so["no_repeat_ngram_size"]))
-        if no_eos and self.eos is not None:
-            sc[:, self.eos] = neg
-        if self.suppress is not None:
-            sc = sc.masked_fill(self.suppress[:d.vocab].bool()[None, :], neg)
-        if mode == 1 and self.begin_suppress is not None:
-            sc = sc.masked_fill(self.begin_suppress[:d.vocab].bool()[None, :], neg)
-        if r is not None:
-            sc = apply_timestamp_rules(sc, self.tokens, n, int(r["begin_index"]), int(r["no_timestamps_token_id"]), self.eos,
-                                       r.get("max_initial_timestamp_index"))
+        sc = processed_scores(logits[:B, :d.vocab], self.tokens, n, begin_index=1 if r is None else r["begin_index"], eos=self.eos,
+                              no_eos=no_eos, first=(mode == 1), suppress=self.suppress, begin_suppress=self.begin_suppress,
+                              timestamp_rules=r, repetition_penalty=so.get("repetition_penalty"),
+                              no_repeat_ngram=so.get("no_repeat_ngram_size") or 0)
         if so.get("do_sample"):
             nxt = warp_and_sample(sc, so.get("temperature"), so.get("top_k"), so.get("top_p"), so.get("generator"))
         else:
@@ -291,24 +313,12 @@ def assist_pick_torch(logits, hist, first_pos, begin_index, eos_token_id=None, m
     """Greedy tokens int64 [B, n] from scores [B, n, V] whose row j predicts the token at sequence index first_pos + j (the torch
     path of oracle.ref_ops, of CPU runs, of unsupported sizes and of DW_ASSIST_TORCH=1; csrc/assist.hip `dw_assist_pick` is the
     kernel).  hist int64 [B, >= first_pos + n - 1]: the sequence those positions continue (history of the timestamp rules);
-    begin_index: decoder prompt length; suppress: f32 [V] with -inf at the suppressed ids, or None."""
-    sc = logits.float()
-    dev = sc.device
-    V = sc.shape[-1]
-    if suppress is not None:
-        sc = sc + suppress
-    if eos_token_id is not None and min_new_tokens > 0 and eos_token_id < V:
-        gen_idx = torch.arange(first_pos - begin_index, first_pos - begin_index + sc.shape[1], device=dev)
-        sc = sc.clone()
-        sc[:, :, eos_token_id] = torch.where((gen_idx < min_new_tokens)[None, :], float("-inf"),
-                                             sc[:, :, eos_token_id])
-    if timestamp_rules is not None:
-        tr = timestamp_rules
-        sc = torch.stack([apply_timestamp_rules(sc[:, j], hist, first_pos + j, int(tr["begin_index"]),
-                                                int(tr["no_timestamps_token_id"]), eos_token_id,
-                                                tr.get("max_initial_timestamp_index"))
-                          for j in range(sc.shape[1])], 1)
-    return sc.argmax(-1)
+    begin_index: decoder prompt length; suppress: a mask of `processed_scores` (an f32 [V] vector with -inf at the suppressed ids reads
+    the same), or None.  No begin-suppress mask, as in the device path."""
+    return torch.stack([processed_scores(logits[:, j], hist, first_pos + j, begin_index=begin_index, eos=eos_token_id,
+                                         no_eos=first_pos + j - begin_index < min_new_tokens, suppress=suppress,
+                                         timestamp_rules=timestamp_rules).argmax(-1)
+                        for j in range(logits.shape[1])], 1)
 
 
 def assist_accept_torch(own, draft, L, k, done, eos_token_id, fill):
@@ -374,19 +384,10 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
                                        eos_token_id, suppress_tokens, int(min_new_tokens), fill, timestamp_rules)
     done = torch.zeros(B, dtype=torch.bool, device=dev)
     drafted = accepted = 0
-    sup = {}
-
-    def sup_mask(V):
-        if not suppress_tokens:
-            return None
-        if V not in sup:
-            m = torch.zeros((V,), dtype=torch.float32, device=dev)
-            m[torch.as_tensor([t for t in suppress_tokens if t < V], dtype=torch.long, device=dev)] = float("-inf")
-            sup[V] = m
-        return sup[V]
+    sup = {V: token_mask(suppress_tokens, V, dev) for V in {dt.vocab, da.vocab}}
 
     def pick(logits, d, first_pos, hist=None):
-        return assist_pick_torch(logits, hist, first_pos, P0, eos_token_id, min_new_tokens, sup_mask(d.vocab), timestamp_rules)
+        return assist_pick_torch(logits, hist, first_pos, P0, eos_token_id, min_new_tokens, sup[d.vocab], timestamp_rules)
 
     def scores_nocache(eng, d, seq, enc, first):
         T = seq.shape[1]
@@ -449,18 +450,10 @@ def _assisted_rounds_device(target, assistant, enc_target, enc_assistant, prompt
     done = torch.zeros((B,), dtype=torch.bool, device=dev) if eos >= 0 else None
     result = torch.zeros((2,), dtype=torch.int32, device=dev)
 
-    def mask(V):                                          # decided once, on the host
-        ids = [int(t) for t in (suppress_tokens or []) if 0 <= int(t) < V]
-        if not ids:
-            return None
-        m = torch.zeros((V,), dtype=torch.uint8, device=dev)
-        m[torch.as_tensor(ids, dtype=torch.long, device=dev)] = 1
-        return m
-
     rk = rule_kwargs(timestamp_rules, eos_token_id)
     rules = dict(min_new=min_new_tokens if eos >= 0 else 0, ts_begin=rk["ts_begin"], max_initial=rk["max_initial"], begin_index=P0,
                  eos=eos)
-    sup_t, sup_a = mask(dt.vocab), mask(da.vocab)
+    sup_t, sup_a = (token_mask(suppress_tokens, d.vocab, dev, torch.uint8) for d in (dt, da))     # decided once, on the host
     ct = target.decode_init(enc_target, B, total)
     ca = assistant.decode_init(enc_assistant, B, total)
     drafted = accepted = 0
@@ -526,15 +519,8 @@ def beam_step_torch(st, logits, cur, cfg):
     neg = BEAM_NEG
     lp = torch.log_softmax(logits.float(), dim=-1)
     flat = running[:, :, :cur].reshape(B * nb, cur)
-    if cur - P < int(cfg["min_new_tokens"]):
-        lp[:, eos] = float("-inf")
-    if cur == P and cfg["bsup"] is not None:
-        lp = lp.masked_fill(cfg["bsup"][None, :], float("-inf"))
-    if cfg["sup"] is not None:
-        lp = lp.masked_fill(cfg["sup"][None, :], float("-inf"))
-    if tr is not None:
-        lp = apply_timestamp_rules(lp, flat, cur, tr["begin_index"], tr["no_timestamps_token_id"], eos,
-                                   tr.get("max_initial_timestamp_index"))
+    lp = processed_scores(lp, flat, cur, begin_index=P, eos=eos, no_eos=cur - P < int(cfg["min_new_tokens"]), first=cur == P,
+                          suppress=cfg["sup"], begin_suppress=cfg["bsup"], timestamp_rules=tr)
     acc = (lp.view(B, nb, V) + run_scores[:, :, None]).reshape(B, nb * V)
     # equal scores go to the lower flat index beam * V + token, as in the kernels: torch.topk leaves their order unspecified, and
     # bf16 logits give one beam's best columns equal scores all the time.  (Twice as many as needed are taken and put in order, so
@@ -613,14 +599,6 @@ def beam_search_decode(engine, enc_out, prompt_ids, max_new_tokens, num_beams, e
     use_kernels = (hasattr(ops, "beam_candidates") and hasattr(ops, "beam_update") and ops.beam_supported(nb, V)
                    and os.environ.get(BEAM_TORCH_ENV, "0") in ("", "0"))
 
-    def mask_of(ids, dtype):                             # decided once, on the host: no per-step `.any()` round trip
-        ids = [int(t) for t in (ids or []) if 0 <= int(t) < V]
-        if not ids:
-            return None
-        m = torch.zeros(V, dtype=dtype, device=dev)
-        m[torch.as_tensor(ids, dtype=torch.long, device=dev)] = 1
-        return m
-
     Lk, D = d.max_src, d.d_model
     enc_rep = enc_out[:B * Lk].view(B, Lk, D).repeat_interleave(nb, 0).reshape(B * nb * Lk, D).contiguous()
     cache = engine.decode_init(enc_rep, B * nb, max_length)
@@ -648,7 +626,7 @@ def beam_search_decode(engine, enc_out, prompt_ids, max_new_tokens, num_beams, e
         return float((c + 1 - P) ** length_penalty), float(hyp_len ** length_penalty)
 
     if use_kernels:
-        sup, bsup = mask_of(suppress_tokens, torch.uint8), mask_of(begin_suppress_tokens, torch.uint8)
+        sup, bsup = (token_mask(ids, V, dev, torch.uint8) for ids in (suppress_tokens, begin_suppress_tokens))
         R = B * nb
         other = dict(running=torch.full_like(running, fill), sequences=torch.full_like(running, fill))
         other["running"][:, :, :P] = prompt_ids[:, None, :]
@@ -678,8 +656,8 @@ def beam_search_decode(engine, enc_out, prompt_ids, max_new_tokens, num_beams, e
             logits = engine.decode_step(next_tok, cache)
     else:
         cfg = dict(P=P, max_length=max_length, nb=nb, V=V, eos=eos, min_new_tokens=int(min_new_tokens),
-                   length_penalty=length_penalty, early_stopping=early_stopping, sup=mask_of(suppress_tokens, torch.bool),
-                   bsup=mask_of(begin_suppress_tokens, torch.bool), timestamp_rules=timestamp_rules)
+                   length_penalty=length_penalty, early_stopping=early_stopping, sup=token_mask(suppress_tokens, V, dev),
+                   bsup=token_mask(begin_suppress_tokens, V, dev), timestamp_rules=timestamp_rules)
         while True:
             src_rows, go_on = beam_step_torch(st, logits[:, :V], cur, cfg)
             reorder(src_rows, cur)

@@ -1154,8 +1154,7 @@ class WhisperForConditionalGeneration(nn.Module):
         import math
         import zlib
         from . import generation as G
-        from .decoding import (SAMPLE_TORCH_ENV, GreedyDecoder, apply_no_repeat_ngram, apply_repetition_penalty,
-                               apply_timestamp_rules)
+        from .decoding import SAMPLE_TORCH_ENV, GreedyDecoder, processed_scores, token_mask
         eng, d = self.engine, self.dims
         B = input_features.shape[0]
         rep_pen = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
@@ -1203,26 +1202,16 @@ class WhisperForConditionalGeneration(nn.Module):
             raise NotImplementedError("token timestamps in the seek loop are implemented for greedy passes (no sampled fallback, "
                                       "assistant or beams) on the MI355X path")
 
-        def vmask(ids):
-            mk = torch.zeros(V, dtype=torch.bool, device=dev)
-            if ids:
-                mk[torch.as_tensor(list(ids), dtype=torch.long, device=dev)] = True
-            return mk
+        def vmask(ids):                                # (all-false where no id names a column: the sampling kernel is given both)
+            mk = token_mask(ids, V, dev)
+            return torch.zeros(V, dtype=torch.bool, device=dev) if mk is None else mk
         sup, bsup = vmask(suppress_tokens), vmask(begin_suppress_tokens)
+        ts_rules = dict(no_timestamps_token_id=nts, max_initial_timestamp_index=max_initial_timestamp_index)
 
         def processed(raw, hist, n, P, min_new):
             """The reference's processed scores of one step: raw f32 [r, V], hist int64 [r, >= n] (n tokens so far)."""
-            sc = raw.clone()
-            if rep_pen is not None:        # GenerationMixin's own processors come first (TF `_get_logits_processor`)
-                sc = apply_repetition_penalty(sc, hist[:, :n], rep_pen)
-            if ngram:
-                sc = apply_no_repeat_ngram(sc, hist[:, :n], ngram)
-            if n - P < min_new:
-                sc[:, eos] = float("-inf")
-            if n == P:
-                sc = sc.masked_fill(bsup[None, :], float("-inf"))
-            sc = sc.masked_fill(sup[None, :], float("-inf"))
-            return apply_timestamp_rules(sc, hist, n, P, nts, eos, max_initial_timestamp_index)
+            return processed_scores(raw, hist, n, begin_index=P, eos=eos, no_eos=n - P < min_new, first=n == P, suppress=sup,
+                                    begin_suppress=bsup, timestamp_rules=ts_rules, repetition_penalty=rep_pen, no_repeat_ngram=ngram)
 
         # the sampled passes select inside the kernel (dw_sample_select) where the ops have it: per step one `exponential_` draw
         # of the shape [r, V] that `torch.multinomial` would draw itself, plus one launch; DW_SAMPLE_TORCH=1 keeps the torch ops
@@ -1600,28 +1589,18 @@ class WhisperForConditionalGeneration(nn.Module):
     def _greedy_no_cache(self, enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress):
         """Greedy search that re-decodes the whole prefix at every step (no KV cache): the cross-check of the cached
         decoder."""
+        from .decoding import processed_scores, token_mask
         eng, d = self.engine, self.dims
         B, dev = ids.shape[0], ids.device
         done = torch.zeros(B, dtype=torch.bool, device=dev)
 
-        def mask(tokens):
-            if not tokens:
-                return None
-            m = torch.zeros(d.vocab, device=dev)
-            m[torch.as_tensor(list(tokens), device=dev)] = float("-inf")
-            return m
-        sup, bsup = mask(suppress), mask(begin_suppress)
+        sup, bsup = (token_mask(t, d.vocab, dev) for t in (suppress, begin_suppress))
         for step in range(max_new):
             T = ids.shape[1]
             logits, _ = eng.decode(ids.contiguous(), enc, save=False)
             sc = logits[: B * T, : d.vocab].view(B, T, -1)[:, -1].float()
-            if eos is not None and step < min_new:
-                sc[:, eos] = float("-inf")
-            if step == 0 and bsup is not None:
-                sc = sc + bsup
-            if sup is not None:
-                sc = sc + sup
-            nxt = sc.argmax(-1)
+            nxt = processed_scores(sc, ids, T, begin_index=T - step, eos=eos, no_eos=step < min_new, first=step == 0, suppress=sup,
+                                   begin_suppress=bsup).argmax(-1)
             if eos is not None:
                 nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
                 done |= nxt == eos

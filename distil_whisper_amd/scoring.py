@@ -18,6 +18,8 @@ through the timestamp mass rule (timestamps together against the best text token
 """
 import torch
 
+from .decoding import rule_kwargs, token_mask
+
 
 class StepScores(tuple):
     """What `GenerateOutput.scores` / `.logits` hold: a tuple with one fp32 [batch, vocab] tensor per generated step, as the
@@ -36,14 +38,6 @@ class StepScores(tuple):
         self = super().__new__(cls, steps)
         self.tokens, self.chosen, self.logprob = tokens, chosen, logprob
         return self
-
-
-def _byte_mask(ids, V, device):
-    if not ids:
-        return None
-    m = torch.zeros(V, dtype=torch.uint8)
-    m[torch.as_tensor(sorted(set(int(i) for i in ids)), dtype=torch.long)] = 1
-    return m.to(device)
 
 
 def score_sequences(model, sequences, enc_out, P, rules, want_scores=True, want_logits=False):
@@ -71,14 +65,12 @@ def score_sequences(model, sequences, enc_out, P, rules, want_scores=True, want_
 
     scores = raw = None
     if want_scores:
-        ts = rules.get("timestamp_rules")
         eos = rules.get("eos_token_id")
-        mi = None if ts is None else ts.get("max_initial_timestamp_index")
-        scores = run(suppress=_byte_mask(rules.get("suppress_tokens"), V, seqs.device),
-                     begin_suppress=_byte_mask(rules.get("begin_suppress_tokens"), V, seqs.device),
-                     min_new=int(rules.get("min_new_tokens") or 0) if eos is not None else 0,
-                     ts_begin=-1 if ts is None else int(ts["no_timestamps_token_id"]) + 1,
-                     max_initial=-1 if mi is None else int(mi), eos=-1 if eos is None else int(eos))
+        rk = rule_kwargs(rules.get("timestamp_rules"), eos)
+        del rk["begin_index"]                      # (the prompt length: `score_tokens` has it as P)
+        scores = run(suppress=token_mask(rules.get("suppress_tokens"), V, seqs.device, torch.uint8),
+                     begin_suppress=token_mask(rules.get("begin_suppress_tokens"), V, seqs.device, torch.uint8),
+                     min_new=int(rules.get("min_new_tokens") or 0) if eos is not None else 0, **rk)
     if want_logits:
         raw = run()
     return scores, raw

@@ -238,25 +238,19 @@ class RefOps:
 
     # GenerationMixin._sample with Whisper's logits processors (TF:generation/logits_process.py, installed by
     # TF:models/whisper/generation_whisper.py:1774-1812): min-new-tokens, begin-suppress, suppress, timestamp rules
-    # (the restatement in distil_whisper_amd.decoding.apply_timestamp_rules is pinned against the transformers class in
-    # tests/test_longform.py), argmax, finished rows filled with the pad token.
+    # (distil_whisper_amd.decoding.processed_scores, pinned against the transformers classes in tests/test_processed_scores.py),
+    # argmax, finished rows filled with the pad token.
     def greedy_select(self, logits, V, tokens, n, cur, *, suppress=None, begin_suppress=None, first=False, no_eos=False,
                       forced=False, ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, fill=-1, done=None):
-        from distil_whisper_amd.decoding import apply_timestamp_rules
+        from distil_whisper_amd.decoding import processed_scores
         B = tokens.shape[0]
         if forced:
             cur.copy_(tokens[:, n].view(B, 1))
             return
-        neg = float("-inf")
-        sc = logits[:B, :V].float()
-        if no_eos and eos >= 0:
-            sc[:, eos] = neg
-        if first and begin_suppress is not None:
-            sc = sc.masked_fill(begin_suppress[:V].bool()[None, :], neg)
-        if suppress is not None:
-            sc = sc.masked_fill(suppress[:V].bool()[None, :], neg)
-        if ts_begin >= 0:
-            sc = apply_timestamp_rules(sc, tokens, n, begin_index, ts_begin - 1, eos, None if max_initial < 0 else max_initial)
+        ts = None if ts_begin < 0 else dict(no_timestamps_token_id=ts_begin - 1,
+                                            max_initial_timestamp_index=None if max_initial < 0 else max_initial)
+        sc = processed_scores(logits[:B, :V], tokens, n, begin_index=begin_index, eos=eos if eos >= 0 else None, no_eos=no_eos,
+                              first=first, suppress=suppress, begin_suppress=begin_suppress, timestamp_rules=ts)
         nxt = sc.argmax(-1)
         if eos >= 0:
             nxt = torch.where(done, torch.full_like(nxt, fill), nxt)
