@@ -96,6 +96,67 @@ extern "C" int dw_greedy_select_history(const void* logits, int B, int V, int64_
     return DW_OK;
 }
 
+// dw_greedy_select_bias: greedy_select_kernel<true> with GenerationMixin's SequenceBiasLogitsProcessor and
+// NoBadWordsLogitsProcessor (`generate(sequence_bias=, bad_words_ids=)`: hot-word boosts and forbidden words) in the same single
+// launch.  In the reference's list the first stands in front of the repetition penalty and the second behind the n-gram rule; a
+// bad word is a bias of -inf, which no later processor brings back, so both are one table (select_rules.h BiasTable) applied in
+// front: thread s tests sequence s against the tail of the row's history, the first entry of a column adds that column's
+// biases up in table order, a -inf sum joins the `banned` bitmap and any other non-zero sum sets the column in a third bitmap,
+// `biased`, which the walk reads like `seen`: a chunk with a bit set is judged column by column as penal?(x + bias), in the
+// mass-rule pass as well.  Nothing is allocated, no other workgroup is waited for, the table is read-only device memory: the
+// step is captured into the per-position graphs like the others.
+// LDS: three bitmaps of 8 KB, the table's columns and sums 4 KB each, 256 B of reduction scratch: 33 024 B per workgroup.
+__global__ __launch_bounds__(SEL_NT) void greedy_select_bias_kernel(
+    const bf16* logits, int V, long ld, const uint8_t* suppress, const uint8_t* begin_suppress, int first, int no_eos,
+    int forced, int tb, int max_initial, int64_t* tokens, long tok_ld, int n, int begin_index, int eos, int fill,
+    uint8_t* done, int64_t* cur, float rep_pen, int ngram, const BiasTable table) {
+    __shared__ Best red[SEL_NT / 64];
+    __shared__ float redf[SEL_NT / 64];
+    __shared__ int redi[SEL_NT / 64];
+    __shared__ unsigned seen[SEL_HIST_V / 32], banned[SEL_HIST_V / 32], biased[SEL_HIST_V / 32];
+    __shared__ int bcol[SEL_BIAS_S];
+    __shared__ float bsum[SEL_BIAS_S];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int64_t* row_tok = tokens + (long)b * tok_ld;
+    if (forced) {                                  // position n still belongs to the forced prefix (teacher forcing)
+        if (tid == 0) cur[b] = row_tok[n];
+        return;
+    }
+    const bf16* row = logits + (long)b * ld;
+    build_history_bitmaps(row_tok, n, V, rep_pen, ngram, seen, banned);
+    build_bias_bitmaps(row_tok, n, V, table, banned, biased, bcol, bsum);
+    const RowRules rr = row_rules(row_tok, n, begin_index, tb, max_initial, V, eos, no_eos, redi);
+    const Best pick = greedy_pick<true, true>(row, V, suppress, begin_suppress, first, rr, seen, banned, rep_pen, red, redf, biased,
+                                              bcol, bsum, table.S);
+    if (tid == 0) {
+        long nxt = pick.i == 0x7fffffff ? 0 : pick.i;
+        if (eos >= 0) {
+            if (done[b]) nxt = fill;
+            if (nxt == eos) done[b] = 1;
+        }
+        row_tok[n] = nxt;
+        cur[b] = nxt;
+    }
+}
+
+extern "C" int dw_greedy_select_bias(const void* logits, int B, int V, int64_t ld, const uint8_t* suppress,
+                                     const uint8_t* begin_suppress, int first, int no_eos, int forced, int ts_begin,
+                                     int max_initial, int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos,
+                                     int fill, uint8_t* done, int64_t* cur, float repetition_penalty, int no_repeat_ngram,
+                                     const int* bias_tok, const int* bias_off, const float* bias_val, int S, void* stream) {
+    DW_CLEAR_ERR();
+    if (!tokens || !cur || B <= 0 || n < 1 || n >= tok_ld) return DW_EINVAL;
+    if (!(repetition_penalty > 0.f) || !(repetition_penalty <= 3.402823466e38f) || no_repeat_ngram < 0) return DW_EINVAL;
+    if (S < 0 || S > SEL_BIAS_S || (S > 0 && (!bias_tok || !bias_off || !bias_val))) return DW_EINVAL;
+    if (!forced && (!select_args_ok(logits, V, ld, n, ts_begin, begin_index, eos) || V > SEL_HIST_V || (eos >= 0 && !done))) return DW_EINVAL;
+    const BiasTable table = {bias_tok, bias_off, bias_val, S};
+    hipLaunchKernelGGL(greedy_select_bias_kernel, dim3(B), dim3(SEL_NT), 0, (hipStream_t)stream, (const bf16*)logits, V,
+                       (long)ld, suppress, begin_suppress, first, no_eos, forced, ts_begin, max_initial, tokens,
+                       (long)tok_ld, n, begin_index, eos, fill, done, cur, repetition_penalty, no_repeat_ngram, table);
+    DW_CHECK_LAUNCH();
+    return DW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Sampled selection (dw_sample_select): `generate(do_sample=True, temperature=, top_k=, top_p=)` in the same single launch.
 // Reference behaviour: TF:generation/utils.py `_get_logits_processor` (processors, then TemperatureLogitsWarper, TopKLogitsWarper,

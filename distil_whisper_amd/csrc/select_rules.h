@@ -2,16 +2,18 @@
 // WhisperTimeStampLogitsProcessor, TF:generation/logits_process.py; RepetitionPenalty / NoRepeatNGram as history bitmaps) for the
 // kernels that apply them -- decode.hip: greedy / history / sampled selection; beam.hip: beam-search candidates; score.hip: scores
 // of finished sequences; assist.hip: the picks of a speculative round -- with the workgroup shape and the (value, index) reduction
-// they share.  A rule changes here and nowhere else: the row state as two allowed id intervals plus two single banned ids (row_rules), the byte masks
-// (rule_masks_of), the history bitmaps (build_history_bitmaps), the clean-chunk test (classify_chunk) and the per-column
-// predicate (column_allowed).  What the kernels keep to themselves is arithmetic: how they hold a row and in which order they sum
-// -- except the kernels that keep only a row's argmax (greedy_select_kernel<false / true>, assist.hip's assist_pick_kernel): their
+// they share.  A rule changes here and nowhere else: the row state as two allowed id intervals plus two single banned ids
+// (row_rules), the byte masks (rule_masks_of), the history bitmaps (build_history_bitmaps), the sequence-bias table
+// (build_bias_bitmaps / bias_of), the clean-chunk test (classify_chunk) and the per-column predicate (column_allowed).  What the
+// kernels keep to themselves is arithmetic: how they hold a row and in which order they sum -- except the kernels that keep
+// only a row's argmax (greedy_select_kernel<false / true>, greedy_select_bias_kernel, assist.hip's assist_pick_kernel): their
 // walk over the row is greedy_pick below, once.
 #pragma once
 #include "common.h"
 
 #define SEL_NT 1024
 #define SEL_HIST_V 65536                            // capacity of a history bitmap in columns (8 KB of LDS each)
+#define SEL_BIAS_S 1024                             // most sequences of a bias table: one thread each (8 KB of LDS)
 
 struct Best { float v; int i; };
 __device__ __forceinline__ Best better(Best a, Best b) {      // larger value wins, ties go to the smaller index
@@ -133,10 +135,62 @@ __device__ __forceinline__ void build_history_bitmaps(const int64_t* row_tok, in
 // bit e: column c0 + e is set in the bitmap (c0 a multiple of 4, below SEL_HIST_V)
 __device__ __forceinline__ unsigned history_bits_of(const unsigned* bitmap, int c0) { return (bitmap[c0 >> 5] >> (c0 & 31)) & 0xfu; }
 
+// The table of SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor (`generate(sequence_bias=, bad_words_ids=)`), flattened by
+// the host (decoding.sequence_bias_table): sequence s is tok[off[s], off[s + 1]) with the bias val[s] for the column of its last
+// token.  The host hands the S <= SEL_BIAS_S sequences (of at most 32 tokens: its cap, no
+// code here depends on a length) over ordered by that column (within a column in the caller's order, the
+// one-token entry first, duplicates of one-token entries already resolved by assignment, `[eos]` bad words already dropped).
+struct BiasTable { const int* tok; const int* off; const float* val; int S; };
+
+// The reference's rule: a sequence of one token always counts; a longer one is ignored when it is longer than the history
+// (len > n), else it counts iff the last len - 1 tokens of the history row_tok[0, n) (decoder prompt included; nothing at or
+// beyond n is read) equal its prefix.  All biases of a column are summed first -- here by the thread of the column's first table
+// entry, over the column's entries in table order (a sequence that does not count adds 0.0, as the reference's `where` does), so
+// the sum does not depend on the arrival order of anything: no floating-point atomics -- and the sum is added to the logit once.
+// On return col[s] holds the column of sequence s (ascending), sum[s] the merged bias where s is the first entry of its column;
+// a column whose sum is -inf is ORed into `banned` (complete before the call: build_history_bitmaps), one whose sum is another
+// non-zero value is set in `biased` (SEL_HIST_V / 32 words, built here).  Called by all SEL_NT threads; col / sum: SEL_BIAS_S
+// entries of LDS each.  (Worst case: all S entries name one column and one thread adds S values, ~1 us per 30 entries.)
+__device__ __forceinline__ void build_bias_bitmaps(const int64_t* row_tok, int n, int V, const BiasTable& t, unsigned* banned,
+                                                   unsigned* biased, int* col, float* sum) {
+    const int tid = threadIdx.x;
+    for (int w = tid; w < SEL_HIST_V / 32; w += SEL_NT) biased[w] = 0u;
+    int c = -1;
+    if (tid < t.S) {
+        const int o0 = t.off[tid], len = t.off[tid + 1] - o0;
+        c = t.tok[o0 + len - 1];
+        bool hit = len <= n;                                            // (n >= 1: a one-token sequence always counts)
+        for (int k = 0; k < len - 1 && hit; ++k) hit = row_tok[n - (len - 1) + k] == (int64_t)t.tok[o0 + k];
+        col[tid] = c;
+        sum[tid] = hit ? t.val[tid] : 0.f;
+    }
+    __syncthreads();
+    if (tid < t.S && (tid == 0 || col[tid - 1] != c)) {                 // the first entry of its column adds the column up
+        float v = sum[tid];
+        for (int s = tid + 1; s < t.S && col[s] == c; ++s) v += sum[s];
+        sum[tid] = v;                                                   // (no other thread reads this column's entries)
+        if (c >= 0 && c < V) {
+            if (v == -INFINITY) atomicOr(&banned[c >> 5], 1u << (c & 31));
+            else if (v != 0.f) atomicOr(&biased[c >> 5], 1u << (c & 31));
+        }
+    }
+    __syncthreads();
+}
+// the merged bias of column c, whose `biased` bit is set: the first table entry of that column (col ascending: lower bound)
+__device__ __forceinline__ float bias_of(const int* col, const float* sum, int S, int c) {
+    int lo = 0, hi = S;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    return sum[lo];
+}
+
 // The four columns c0 .. c0 + 3 (c0 a multiple of 4) as a whole.  clean: all four exist (`live`: the chunk is no clamped repeat
 // of the row's last one), lie inside ONE allowed interval, and no mask byte, banned id or history bit (sbits / bbits of
-// history_bits_of: seen / banned; 0 without history rules) names any of them -- each column then keeps its logit and counts as
-// text (in_text) or timestamp.  A chunk that is not clean is judged column by column with column_allowed.
+// history_bits_of: seen -- or biased, which reads the same here -- / banned; 0 without history rules) names any of them -- each
+// column then keeps its logit and counts as text (in_text) or timestamp.  A chunk that is not clean is judged column by column
+// with column_allowed.
 struct ChunkKind { bool clean, in_text; };
 __device__ __forceinline__ ChunkKind classify_chunk(const RowRules& r, unsigned mask, bool live, int c0, int V, unsigned sbits = 0,
                                                     unsigned bbits = 0) {
@@ -164,16 +218,20 @@ __device__ __forceinline__ bool column_allowed(const RowRules& r, int c0, int e,
 // `first` (tested at each use: with the pointer nulled instead greedy_select_kernel<true> ran 0.15 us slower,
 // profiles/greedy_walk_refactor.md); HIST: seen / banned are the complete bitmaps of build_history_bitmaps and a seen column
 // takes RepetitionPenaltyLogitsProcessor's v < 0 ? v * rep_pen : v / rep_pen (all three unused without HIST); red / redf:
-// SEL_NT / 64 entries of LDS each.
+// SEL_NT / 64 entries of LDS each.  BIAS (with HIST): biased / bcol / bsum / S are what build_bias_bitmaps left -- a biased
+// column is judged as penal?(x + bias): SequenceBiasLogitsProcessor stands in front of the repetition penalty in the reference's
+// list, and the banned bitmap already holds the bad words -- in both passes; the instances without BIAS compile as before.
 // Pass 1 keeps the best allowed text token and the best allowed timestamp token, pass 2 (timestamp rules only) sums the
 // timestamp probability mass for the "timestamps together beat the best text token" rule.  A row lives on ONE CU (one
 // workgroup), so the walk is bound by instructions per column, not by bytes: a chunk of four columns that classify_chunk calls
 // clean (almost every chunk) takes the short path of `judge` -- a compare and two selects per column; ascending order within a
 // thread makes the strict compare keep the smallest index among equal values, better() does the same everywhere else.
-template <bool HIST>
+template <bool HIST, bool BIAS = false>
 __device__ __forceinline__ Best greedy_pick(const bf16* row, int V, const uint8_t* suppress, const uint8_t* begin_suppress, int first,
                                             const RowRules& rr, const unsigned* seen, const unsigned* banned, float rep_pen,
-                                            Best* red, float* redf) {
+                                            Best* red, float* redf, const unsigned* biased = nullptr, const int* bcol = nullptr,
+                                            const float* bsum = nullptr, int S = 0) {
+    static_assert(HIST || !BIAS, "the bias table comes with the history bitmaps");
     const int tid = threadIdx.x;
     const int tsb = rr.tsb;
     auto penal = [&](float v) -> float { return v < 0.f ? v * rep_pen : v / rep_pen; };
@@ -189,8 +247,10 @@ __device__ __forceinline__ Best greedy_pick(const bf16* row, int V, const uint8_
     Best bt = {-INFINITY, 0x7fffffff}, bs = {-INFINITY, 0x7fffffff};
     auto judge = [&](int c0, const bf16x4& x, unsigned mask, bool live) {
         unsigned sbits = 0, bbits = 0;                 // bit e: column c0 + e is in the history / banned
+        unsigned xbits = 0;                            // bit e: column c0 + e takes a bias
         if constexpr (HIST) { sbits = history_bits_of(seen, c0); bbits = history_bits_of(banned, c0); }
-        const ChunkKind kind = classify_chunk(rr, mask, live, c0, V, sbits, bbits);
+        if constexpr (BIAS) xbits = history_bits_of(biased, c0);
+        const ChunkKind kind = classify_chunk(rr, mask, live, c0, V, sbits | xbits, bbits);
         if (kind.clean) {
             const bool in_text = kind.in_text;
             float bv = in_text ? bt.v : bs.v;
@@ -208,6 +268,7 @@ __device__ __forceinline__ Best greedy_pick(const bf16* row, int V, const uint8_
             const int c = c0 + e;
             if (column_allowed(rr, c0, e, V, mask, bbits, live)) {
                 float v = bf2f(x[e]);
+                if constexpr (BIAS) { if ((xbits >> e) & 1u) v += bias_of(bcol, bsum, S, c); }
                 if constexpr (HIST) { if ((sbits >> e) & 1u) v = penal(v); }
                 const Best cand = {v, c};
                 if (c < tsb) bt = better(bt, cand); else bs = better(bs, cand);
@@ -244,6 +305,7 @@ __device__ __forceinline__ Best greedy_pick(const bf16* row, int V, const uint8_
         for (int c = tsb + tid; c < V; c += SEL_NT)
             if (allowed(c)) {
                 float v = bf2f(row[c]);
+                if constexpr (BIAS) { if ((biased[c >> 5] >> (c & 31)) & 1u) v += bias_of(bcol, bsum, S, c); }
                 if constexpr (HIST) { if ((seen[c >> 5] >> (c & 31)) & 1u) v = penal(v); }
                 sum += __expf(v - bs.v);
             }

@@ -87,6 +87,130 @@ def apply_no_repeat_ngram(scores, input_ids, n):
     return scores.masked_fill(ban_any, float("-inf"))
 
 
+# caps of the selection kernel's bias table, stated here once: sequences (csrc/select_rules.h SEL_BIAS_S: one thread each, the C
+# entry refuses more) and tokens per sequence (a host cap only: the kernel compares any length up to the history's)
+SEQUENCE_BIAS_MAX_SEQUENCES, SEQUENCE_BIAS_MAX_TOKENS = 1024, 32
+
+
+class SequenceBiasTable:
+    """`sequence_bias` / `bad_words_ids` of one `generate` call, validated and flattened (`sequence_bias_table`): seqs -- tuples
+    of token ids -- and vals -- their biases, -inf for a bad word -- in TABLE ORDER: ascending by the column (last token), within
+    a column the one-token entry first, then the caller's order, bad words last.  That is the order in which the reference adds
+    a column's biases up (`length_1_bias` first, then the dict's order; NoBadWords is a later processor), so the sum is the
+    reference's bit for bit.  `tensors(device)`: tok int32 [T], off int32 [S + 1], val f32 [S] for `greedy_select_bias`.
+    Hashable by content (a decoder is cached under its options)."""
+
+    def __init__(self, seqs, vals):
+        self.seqs, self.vals = tuple(tuple(int(t) for t in q) for q in seqs), tuple(float(v) for v in vals)
+        self.S = len(self.seqs)
+        self._dev = {}
+
+    def __eq__(self, other):
+        return isinstance(other, SequenceBiasTable) and (self.seqs, self.vals) == (other.seqs, other.vals)
+
+    def __hash__(self):
+        return hash((self.seqs, self.vals))
+
+    def __repr__(self):
+        return f"SequenceBiasTable({self.S} sequences)"
+
+    def tensors(self, device):
+        key = str(device)
+        if key not in self._dev:
+            off = [0]
+            for q in self.seqs:
+                off.append(off[-1] + len(q))
+            self._dev[key] = dict(
+                bias_tok=torch.tensor([t for q in self.seqs for t in q], dtype=torch.int32, device=device),
+                bias_off=torch.tensor(off, dtype=torch.int32, device=device),
+                bias_val=torch.tensor(self.vals, dtype=torch.float32, device=device))
+        return self._dev[key]
+
+
+def sequence_bias_table(sequence_bias, bad_words_ids, vocab, eos_token_id=None):
+    """`generate(sequence_bias=, bad_words_ids=)` -> SequenceBiasTable, or None when neither names a sequence.  Host only.  It
+    refuses everything the reference refuses, with the reference's messages, and MORE, EARLIER: an empty token list, a list-form
+    element that is no (tokens, bias) pair -- the reference lets those through and fails inside its first step -- and an id >= vocab,
+    which the reference reports at its first step, are refused here before anything is decoded.  The checks it shares are the reference's (`SequenceBiasLogitsProcessor._validate_arguments` / `_prepare_bias_variables`,
+    `NoBadWordsLogitsProcessor`, TF:generation/logits_process.py): the list form becomes a dict -- a repeated sequence keeps its
+    first place and its last bias, which is also how one-token duplicates end up ASSIGNED, not summed --, bad words that are
+    exactly `[eos]` are dropped, an id >= vocab raises.  Beyond the kernel's caps (1024 sequences of at most 32 tokens) and for a
+    bias that is NaN or +inf: NotImplementedError."""
+    import numpy as np
+    is_id = lambda t: isinstance(t, (int, np.integer))                                  # noqa: E731
+    entries = []                                                                        # (sequence, bias, rank within a column)
+    if sequence_bias is not None:
+        sb = sequence_bias
+        if not isinstance(sb, dict) and not isinstance(sb, list) or len(sb) == 0:
+            raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb}.")
+        if isinstance(sb, dict):
+            if any(not isinstance(q, tuple) for q in sb):
+                raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb}.")
+            if any(any(not is_id(t) or t < 0 for t in q) or len(q) == 0 for q in sb):
+                raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sb}.")
+            if any(not isinstance(v, float) for v in sb.values()):
+                raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sb}.")
+            as_dict = dict(sb)
+        else:
+            def pair_ok(e):
+                return (isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], list) and len(e[0]) > 0
+                        and all(is_id(t) and t > 0 for t in e[0]) and isinstance(e[1], float))
+            if any(not pair_ok(e) for e in sb):
+                raise ValueError("Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and "
+                                 f"float, but is {sb}.")
+            as_dict = {tuple(e[0]): e[1] for e in sb}
+        entries += [(q, v, 0 if len(q) == 1 else 1) for q, v in as_dict.items()]
+    if bad_words_ids is not None:
+        bw = bad_words_ids
+        if not isinstance(bw, list) or len(bw) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw}.")
+        if any(not isinstance(q, list) for q in bw):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw}.")
+        if any(any(not is_id(t) or t < 0 for t in q) for q in bw):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bw}.")
+        if any(len(q) == 0 for q in bw):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bw}.")
+        eos = [] if eos_token_id is None else ([int(eos_token_id)] if is_id(eos_token_id) else [int(t) for t in eos_token_id])
+        entries += [(q, float("-inf"), 2) for q in {tuple(q): None for q in bw if not any(list(q) == [e] for e in eos)}]
+    for _, group in ((0, [e for e in entries if e[2] < 2]), (1, [e for e in entries if e[2] == 2])):   # (per processor, as there)
+        invalid = [t for q, _, _ in group for t in q if t >= vocab]
+        if invalid:
+            raise ValueError(f"The model vocabulary size is {vocab}, but the following tokens were being biased: {invalid}")
+    if not entries:
+        return None
+    if len(entries) > SEQUENCE_BIAS_MAX_SEQUENCES or any(len(q) > SEQUENCE_BIAS_MAX_TOKENS for q, _, _ in entries):
+        raise NotImplementedError(
+            f"sequence_bias / bad_words_ids: at most {SEQUENCE_BIAS_MAX_SEQUENCES} sequences of at most {SEQUENCE_BIAS_MAX_TOKENS} "
+            f"tokens each are implemented on the MI355X path (got {len(entries)} sequences, the longest of "
+            f"{max(len(q) for q, _, _ in entries)} tokens)")
+    if any(v != v or v == float("inf") for _, v, _ in entries):
+        raise NotImplementedError("sequence_bias: a bias of NaN or +inf is not implemented on the MI355X path")
+    order = sorted(range(len(entries)), key=lambda i: (entries[i][0][-1], entries[i][2], i))
+    return SequenceBiasTable([entries[i][0] for i in order], [entries[i][1] for i in order])
+
+
+def apply_sequence_bias(scores, input_ids, table):
+    """`SequenceBiasLogitsProcessor` and `NoBadWordsLogitsProcessor` (TF:generation/logits_process.py) on scores f32 [rows, V] with
+    the history input_ids int64 [rows, n] (decoder prompt included), table: SequenceBiasTable.  The reference's rule to the letter:
+    a one-token sequence always counts; a longer one is ignored when len(sequence) > n, else it counts iff the last len - 1 tokens
+    of the history equal its prefix; the biases that count are summed per column first (a sequence that does not count adds 0.0)
+    and the sum is added to the scores once.  A bad word is a bias of -inf: its processor stands behind the repetition rules in
+    the reference's list, but nothing brings a -inf back, so one pass in front gives the same scores."""
+    n = input_ids.shape[1]
+    bias = torch.zeros_like(scores)
+    zero = torch.zeros((), dtype=scores.dtype, device=scores.device)
+    for seq, v in zip(table.seqs, table.vals):
+        if len(seq) == 1:
+            bias[:, seq[0]] += v
+            continue
+        if len(seq) > n:
+            continue
+        pre = torch.tensor(seq[:-1], dtype=input_ids.dtype, device=input_ids.device)
+        match = (input_ids[:, n - len(pre):] == pre[None, :]).all(1)
+        bias[:, seq[-1]] += torch.where(match, torch.full_like(zero, v), zero)
+    return scores + bias
+
+
 def warp_and_sample(scores, temperature=None, top_k=None, top_p=None, generator=None):
     """The sampling tail of `GenerationMixin._sample`: TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper (in
     that order, TF `_get_logits_processor`), softmax, one `torch.multinomial` draw per row."""
@@ -128,9 +252,10 @@ def token_mask(ids, V, device, dtype=torch.bool):
 
 
 def processed_scores(scores, hist, n, *, begin_index, eos=None, no_eos=False, first=False, suppress=None, begin_suppress=None,
-                     timestamp_rules=None, repetition_penalty=None, no_repeat_ngram=0):
+                     timestamp_rules=None, repetition_penalty=None, no_repeat_ngram=0, sequence_bias=None):
     """The scores of one step after the reference's logits processors, in its order (TF `_get_logits_processor`, then
-    TF:generation_whisper.py:1774-1812): RepetitionPenalty, NoRepeatNGram, MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens,
+    TF:generation_whisper.py:1774-1812): SequenceBias (with NoBadWords: `sequence_bias`, a SequenceBiasTable or None,
+    `apply_sequence_bias`), RepetitionPenalty, NoRepeatNGram, MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens,
     WhisperTimeStamp -> f32 [rows, V].  This is the one torch statement of what the selection kernels judge (csrc/select_rules.h):
     every torch path of the package and oracle.ref_ops select from it.  scores [rows, V] (logits, or their log-softmax under beam
     search; left unchanged); hist int64 [rows, >= n] of which the first n are the sequence so far, decoder prompt of `begin_index`
@@ -140,6 +265,8 @@ def processed_scores(scores, hist, n, *, begin_index, eos=None, no_eos=False, fi
     neg = float("-inf")
     V = scores.shape[-1]
     sc = scores.float()
+    if sequence_bias is not None:
+        sc = apply_sequence_bias(sc, hist[:, :n], sequence_bias)
     if repetition_penalty is not None and float(repetition_penalty) != 1.0:
         sc = apply_repetition_penalty(sc, hist[:, :n], float(repetition_penalty))
     if no_repeat_ngram:
@@ -191,18 +318,28 @@ class GreedyDecoder:
         # `argmax(probs / q)` with `q = empty_like(probs).exponential_(1, generator=g)` on every device, so the only torch op
         # left is that `exponential_` into the static `noise` buffer [B, V] -- the shape of `probs`, so the generator advances as
         # on the torch path --, launched in front of every replay: outside the graph, hence no graph-safe generator registration.
+        # soft["sequence_bias"] (a SequenceBiasTable: `generate(sequence_bias=, bad_words_ids=)`): greedy decoding applies it, with
+        # the two history rules, inside the selection kernel (dw_greedy_select_bias; the table is three static device tensors, so
+        # the step is captured like the others); sampling with a table takes the torch ops.
         # On ops without these entries (the torch restatement oracle.ref_ops), or with DW_SAMPLE_TORCH=1 for sampling, the
         # selection runs as torch ops on the step's logits, eagerly, without HIP-graph replay.
         # Generator state: both paths draw once per generated position and leave the loop at the same `check_every` boundary, so
         # they consume the generator identically; nothing has to be restored.
         self.soft = soft
         self.history = None
+        self.bias = None
         self.sample = None
         self.noise = None
         if soft is not None:
             rp, ng = soft.get("repetition_penalty"), int(soft.get("no_repeat_ngram_size") or 0)
             rp = 1.0 if rp is None else float(rp)
-            if not soft.get("do_sample") and (rp != 1.0 or ng) and hasattr(engine.ops, "greedy_select_history"):
+            table = soft.get("sequence_bias")
+            if table is not None:
+                if not soft.get("do_sample") and hasattr(engine.ops, "greedy_select_bias"):
+                    self.bias = dict(repetition_penalty=rp, no_repeat_ngram=ng, **table.tensors(dev))
+                else:
+                    self.use_graphs = False
+            elif not soft.get("do_sample") and (rp != 1.0 or ng) and hasattr(engine.ops, "greedy_select_history"):
                 self.history = dict(repetition_penalty=rp, no_repeat_ngram=ng)
             elif soft.get("do_sample") and hasattr(engine.ops, "sample_select") and os.environ.get(SAMPLE_TORCH_ENV, "0") in ("", "0"):
                 t, k, p = soft.get("temperature"), soft.get("top_k"), soft.get("top_p")
@@ -221,7 +358,7 @@ class GreedyDecoder:
         eng, d = self.eng, self.eng.dims
         self.cache["t"] = t
         logits = eng.decode_step(self.cur, self.cache)
-        if self.soft is not None and self.history is None and self.sample is None and mode != 0:
+        if self.soft is not None and self.history is None and self.sample is None and self.bias is None and mode != 0:
             self._select_soft(logits, t + 1, mode, no_eos)
             return
         # logits processors of the reference (min-new-tokens, begin-suppress, suppress, timestamp rules), the choice of the
@@ -232,6 +369,8 @@ class GreedyDecoder:
         if self.sample is not None and mode != 0:
             # (`noise` holds this position's draw: `_run_step` filled it just before this launch / this graph's replay)
             ops.sample_select(*args, self.noise, **common, **self.sample)
+        elif self.bias is not None:
+            ops.greedy_select_bias(*args, forced=(mode == 0), **common, **self.bias)
         elif self.history is not None:
             ops.greedy_select_history(*args, forced=(mode == 0), **common, **self.history)
         else:
@@ -244,7 +383,7 @@ class GreedyDecoder:
         sc = processed_scores(logits[:B, :d.vocab], self.tokens, n, begin_index=1 if r is None else r["begin_index"], eos=self.eos,
                               no_eos=no_eos, first=(mode == 1), suppress=self.suppress, begin_suppress=self.begin_suppress,
                               timestamp_rules=r, repetition_penalty=so.get("repetition_penalty"),
-                              no_repeat_ngram=so.get("no_repeat_ngram_size") or 0)
+                              no_repeat_ngram=so.get("no_repeat_ngram_size") or 0, sequence_bias=so.get("sequence_bias"))
         if so.get("do_sample"):
             nxt = warp_and_sample(sc, so.get("temperature"), so.get("top_k"), so.get("top_p"), so.get("generator"))
         else:

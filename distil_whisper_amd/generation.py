@@ -51,7 +51,8 @@ _CONFIG_KEYS = ("max_length", "max_new_tokens", "min_new_tokens", "num_beams", "
                 "forced_decoder_ids", "num_return_sequences", "use_cache", "output_scores", "output_logits",
                 "return_dict_in_generate",
                 "num_assistant_tokens", "prompt_condition_type", "length_penalty", "repetition_penalty",
-                "no_repeat_ngram_size", "temperature", "early_stopping", "num_beam_groups", "alignment_heads")
+                "no_repeat_ngram_size", "temperature", "early_stopping", "num_beam_groups", "alignment_heads",
+                "sequence_bias", "bad_words_ids")
 
 
 class GenerationConfig:

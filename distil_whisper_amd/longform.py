@@ -200,18 +200,26 @@ def two_stage_pipeline(owner, ops, dev, batches, encode_fn, decode_fn, overlap, 
         main.wait_stream(s_dec)
 
 
-def history_soft(repetition_penalty, no_repeat_ngram_size):
-    """The `soft` argument of decoding.GreedyDecoder for greedy decoding under `repetition_penalty` / `no_repeat_ngram_size`
-    (None when both are off)."""
+def history_soft(repetition_penalty, no_repeat_ngram_size, sequence_bias=None, bad_words_ids=None, vocab=None, eos_token_id=None):
+    """The `soft` argument of decoding.GreedyDecoder for greedy decoding under `repetition_penalty` / `no_repeat_ngram_size` and
+    `sequence_bias` / `bad_words_ids` (validated and flattened by decoding.sequence_bias_table for a vocabulary of `vocab` ids);
+    None when all are off."""
     rp = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
     ng = int(no_repeat_ngram_size or 0)
     if rp is not None and not rp > 0.0:
         raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
     if ng < 0:
         raise ValueError(f"`no_repeat_ngram_size` has to be a positive integer or 0, but is {no_repeat_ngram_size}")
-    if rp is None and not ng:
+    table = None
+    if sequence_bias is not None or bad_words_ids is not None:
+        from .decoding import sequence_bias_table
+        table = sequence_bias_table(sequence_bias, bad_words_ids, vocab, eos_token_id)
+    if rp is None and not ng and table is None:
         return None
-    return dict(do_sample=False, repetition_penalty=rp, no_repeat_ngram_size=ng)
+    soft = dict(do_sample=False, repetition_penalty=rp, no_repeat_ngram_size=ng)
+    if table is not None:
+        soft["sequence_bias"] = table
+    return soft
 
 
 class LongFormTranscriber:
@@ -221,9 +229,11 @@ class LongFormTranscriber:
                  max_new_tokens=128, prompt_ids=None, eos_token_id=None, first_special_id=None, suppress_tokens=None,
                  begin_suppress_tokens=None, use_graphs=None, rank=0, world=1, return_timestamps=False,
                  no_timestamps_token_id=None, max_initial_timestamp_index=50, special_ids=None, overlap=False,
-                 decode_cus=64, repetition_penalty=None, no_repeat_ngram_size=0):
+                 decode_cus=64, repetition_penalty=None, no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None):
         """repetition_penalty / no_repeat_ngram_size: GenerationMixin's two rules against repetition loops, applied per window
         by the selection kernel inside the graph-captured token step (decoding.GreedyDecoder `soft`).
+        sequence_bias / bad_words_ids: GenerationMixin's hot-word boosts and forbidden words (`generate` says how they are
+        written), applied per window by the same launch; the history they are matched against is the window's own.
         return_timestamps=True: the windows are decoded under the timestamp rules (`prompt_ids` must then not end in
         <|notimestamps|>; `no_timestamps_token_id` is required) and stitched by their timestamp tokens; the call returns
         per utterance a list of {"timestamp": (start, end), "tokens": [...]} (`stitch_timestamped`)."""
@@ -274,7 +284,8 @@ class LongFormTranscriber:
         self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
                                      suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
                                      use_graphs=use_graphs, timestamp_rules=rules,
-                                     soft=history_soft(repetition_penalty, no_repeat_ngram_size))
+                                     soft=history_soft(repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids,
+                                                       d.vocab, eos_token_id))
         self._wave = torch.zeros((self.B, feature_extractor.n_samples), dtype=torch.float32, device=dev)
         # overlap=True (GPU only): the encoder of batch i+1 runs on one HIP stream while the token loop of batch i runs on
         # another.  A batch of 16 windows is ~41 ms of encoder (MFMA-bound, persistent GEMM grids on every CU) followed by ~32 ms

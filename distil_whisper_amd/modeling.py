@@ -795,6 +795,11 @@ class WhisperForConditionalGeneration(nn.Module):
         `compression_ratio_threshold`, `logprob_threshold`) and the `no_speech_threshold` skip.
         Greedy decoding also takes GenerationMixin's `repetition_penalty` and `no_repeat_ngram_size`, in one window and in the
         seek loop: the selection kernel applies them (dw_greedy_select_history), so `use_graphs=True` holds with them.
+        `sequence_bias` / `bad_words_ids` (SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor: hot-word boosts and forbidden
+        words; at most 1024 sequences of at most 32 tokens): greedy decoding, in one window and in the seek loop, applies them in
+        the same selection launch (dw_greedy_select_bias), so `use_graphs=True` holds; the seek loop's sampled fallback passes
+        apply them as torch ops.  Combined with beams, an assistant, plain sampling, `use_cache=False`, `output_scores` /
+        `output_logits`, `return_token_timestamps`, or `condition_on_prev_tokens=True` over several utterances they RAISE.
         Single-window decoding takes plain sampling as well (a positive `temperature`, as in the reference's
         generate_with_fallback, with `top_k` / `top_p`): decoding.GreedyDecoder `soft`.  The selection kernel samples as well
         (dw_sample_select: processors, warpers and the draw in one launch on Exponential(1) noise that torch's generator draws,
@@ -856,11 +861,37 @@ class WhisperForConditionalGeneration(nn.Module):
         # top-p sampling): on the single-call KV-cache decoder (decoding.GreedyDecoder `soft`); elsewhere they raise below
         soft = None
         rp, nrn = getattr(gc, "repetition_penalty", None), int(getattr(gc, "no_repeat_ngram_size", 0) or 0)
-        if sample_temp is not None or rp not in (None, 1.0) or nrn:
+        # sequence_bias / bad_words_ids (SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor): validated and flattened on the
+        # host, applied by the selection kernel of greedy decoding (decoding.GreedyDecoder `soft`); elsewhere they raise
+        bias_table = None
+        if getattr(gc, "sequence_bias", None) is not None or getattr(gc, "bad_words_ids", None) is not None:
+            from .decoding import sequence_bias_table
+            bias_table = sequence_bias_table(getattr(gc, "sequence_bias", None), getattr(gc, "bad_words_ids", None), d.vocab,
+                                             gc.eos_token_id)
+        if bias_table is not None:
+            n_utt = (input_features if input_features is not None else kwargs.get("encoder_outputs"))
+            n_utt = n_utt.shape[0] if torch.is_tensor(n_utt) and n_utt.dim() == 3 else None
+            for on, combo in ((num_beams > 1, "beam search (num_beams > 1)"),
+                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
+                              (sample_temp is not None, "plain sampling (a positive temperature)"),
+                              (kwargs.get("use_cache", True) is False, "use_cache=False"),
+                              (bool(return_dict_in_generate or getattr(gc, "return_dict_in_generate", False)) and
+                               (bool(getattr(gc, "output_scores", False)) or bool(getattr(gc, "output_logits", False))),
+                               "output_scores / output_logits"),
+                              (bool(return_token_timestamps), "return_token_timestamps"),
+                              (bool(condition_on_prev_tokens) and n_utt is not None and n_utt > 1,
+                               "condition_on_prev_tokens=True over several utterances (the reference left-pads that batch with "
+                               "pad_token_id and its processors count the pads as history; pass one utterance per call)")):
+                if on:
+                    raise NotImplementedError(f"sequence_bias / bad_words_ids combined with {combo} are not implemented on the "
+                                              "MI355X path (they are applied by the selection kernel of greedy decoding)")
+        if sample_temp is not None or rp not in (None, 1.0) or nrn or bias_table is not None:
             # (an unset top_k is GenerationMixin's global default of 50 when sampling; run_eval.py:739 passes top_k=0 = off)
             tk = getattr(gc, "top_k", None)
             soft = dict(do_sample=sample_temp is not None, temperature=sample_temp, top_k=50 if tk is None else tk,
                         top_p=getattr(gc, "top_p", None), repetition_penalty=rp, no_repeat_ngram_size=nrn)
+            if bias_table is not None:
+                soft["sequence_bias"] = bias_table
             if num_beams > 1 or kwargs.get("assistant_model") is not None or kwargs.get("use_cache", True) is False:
                 raise NotImplementedError("sampling / repetition_penalty / no_repeat_ngram_size are implemented for greedy "
                                           "single-window decoding with the KV cache (not with beams, an assistant or use_cache=False)")
@@ -942,7 +973,8 @@ class WhisperForConditionalGeneration(nn.Module):
                 return self._generate_seek_loop(input_features, attention_mask, gc, language, task, is_multilingual,
                                                 prompt_ids, kwargs, use_graphs, return_dict_in_generate, num_beams,
                                                 fallback_args, return_segments, token_ts,
-                                                history=dict(repetition_penalty=rp, no_repeat_ngram_size=nrn))
+                                                history=dict(repetition_penalty=rp, no_repeat_ngram_size=nrn,
+                                                             sequence_bias=bias_table))
             if return_segments:
                 raise NotImplementedError("return_segments comes with the timestamp seek loop (return_timestamps=True) "
                                           "on the MI355X path")
@@ -1101,7 +1133,8 @@ class WhisperForConditionalGeneration(nn.Module):
                     detect_language=None, temperatures=(0.0,), compression_ratio_threshold=None, logprob_threshold=None,
                     no_speech_threshold=None, condition_on_prev_tokens=False, prev_sot_token_id=None, prompt_ids=None,
                     prompt_all_segments=False, num_beams=1, length_penalty=1.0, early_stopping=False, assistant=None,
-                    num_assistant_tokens=5, token_timestamps=None, repetition_penalty=None, no_repeat_ngram_size=0):
+                    num_assistant_tokens=5, token_timestamps=None, repetition_penalty=None, no_repeat_ngram_size=0,
+                    sequence_bias=None):
         """The seek loop itself (TF:generation_whisper.py:784-903): input_features [B, n_mels, frames], max_frames[b] =
         valid mel frames of utterance b.  init_tokens: the decoder prompt rows (list of B lists) or a callable(detect)
         building them (detect() = language ids from the first window); lengths(P) -> (max_new_tokens, min_new_tokens)
@@ -1150,6 +1183,10 @@ class WhisperForConditionalGeneration(nn.Module):
             sampled fallback passes apply them in the sampling kernel (or through `processed` on the torch path) and the
             threshold scores see them through `processed`.  Not with beams or an assistant,
             and not with condition_on_prev_tokens over several utterances (see the message below).
+          * sequence_bias (a decoding.SequenceBiasTable: `generate(sequence_bias=, bad_words_ids=)`): under the same conditions;
+            the greedy pass of a window applies the table inside the selection kernel (dw_greedy_select_bias), the sampled
+            fallback passes and the threshold scores apply it as torch ops through `processed` (the sampling kernel takes no
+            table).  Not with token timestamps.
         -> per utterance the list of segments {"start", "end", "tokens"}."""
         import math
         import zlib
@@ -1160,6 +1197,16 @@ class WhisperForConditionalGeneration(nn.Module):
         rep_pen = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
         ngram = int(no_repeat_ngram_size or 0)
         hist_soft = None
+        if sequence_bias is not None:
+            if int(num_beams) > 1 or assistant is not None or token_timestamps is not None:
+                raise NotImplementedError("sequence_bias / bad_words_ids inside the timestamp seek loop are implemented for greedy "
+                                          "passes (not with beams, an assistant or token timestamps) on the MI355X path")
+            if condition_on_prev_tokens and B > 1:
+                raise NotImplementedError(
+                    "sequence_bias / bad_words_ids with condition_on_prev_tokens=True and more than one utterance are not "
+                    "implemented on the MI355X path: the reference left-pads that batch with pad_token_id and its processors "
+                    "then count the pads as history, while this package decodes rows in groups of equal prompt length (no "
+                    "pads).  Pass one utterance per call")
         if rep_pen is not None or ngram:
             if int(num_beams) > 1 or assistant is not None:
                 raise NotImplementedError("repetition_penalty / no_repeat_ngram_size inside the timestamp seek loop are "
@@ -1171,6 +1218,9 @@ class WhisperForConditionalGeneration(nn.Module):
                     "processors then count the pads as history, while this package decodes rows in groups of equal prompt "
                     "length (no pads).  Pass one utterance per call")
             hist_soft = dict(do_sample=False, repetition_penalty=rep_pen, no_repeat_ngram_size=ngram)
+        if sequence_bias is not None:
+            hist_soft = dict(hist_soft or dict(do_sample=False, repetition_penalty=rep_pen, no_repeat_ngram_size=ngram),
+                             sequence_bias=sequence_bias)
         dev = input_features.device
         W, V = 2 * d.max_src, d.vocab
         feats = input_features.to(torch.float32)
@@ -1211,11 +1261,14 @@ class WhisperForConditionalGeneration(nn.Module):
         def processed(raw, hist, n, P, min_new):
             """The reference's processed scores of one step: raw f32 [r, V], hist int64 [r, >= n] (n tokens so far)."""
             return processed_scores(raw, hist, n, begin_index=P, eos=eos, no_eos=n - P < min_new, first=n == P, suppress=sup,
-                                    begin_suppress=bsup, timestamp_rules=ts_rules, repetition_penalty=rep_pen, no_repeat_ngram=ngram)
+                                    begin_suppress=bsup, timestamp_rules=ts_rules, repetition_penalty=rep_pen, no_repeat_ngram=ngram,
+                                    sequence_bias=sequence_bias)
 
         # the sampled passes select inside the kernel (dw_sample_select) where the ops have it: per step one `exponential_` draw
         # of the shape [r, V] that `torch.multinomial` would draw itself, plus one launch; DW_SAMPLE_TORCH=1 keeps the torch ops
-        sample_kernel = hasattr(eng.ops, "sample_select") and os.environ.get(SAMPLE_TORCH_ENV, "0") in ("", "0")
+        # (the sampling kernel takes no bias table: with one the sampled passes are the torch ops of `processed`)
+        sample_kernel = hasattr(eng.ops, "sample_select") and os.environ.get(SAMPLE_TORCH_ENV, "0") in ("", "0") and \
+            sequence_bias is None
 
         def sample(enc, ids, max_new, min_new, temp):
             """Multinomial sampling at temperature `temp` over the processed scores (fallback passes)."""
@@ -1375,7 +1428,7 @@ class WhisperForConditionalGeneration(nn.Module):
                         out = out[:, P:].tolist()
                     else:
                         key = (len(pending), P, max_new, eos, pad, nts, max_initial_timestamp_index,
-                               tuple(suppress_tokens or ()), tuple(begin_suppress_tokens or ()), rep_pen, ngram)
+                               tuple(suppress_tokens or ()), tuple(begin_suppress_tokens or ()), rep_pen, ngram, sequence_bias)
                         dec = decoders.get(key)
                         if dec is None:
                             if len(decoders) >= 4:     # (a decoder owns its K/V caches: keep a handful alive)

@@ -11,6 +11,8 @@ import os
 
 import torch
 
+from .decoding import SEQUENCE_BIAS_MAX_SEQUENCES, SEQUENCE_BIAS_MAX_TOKENS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdwamd.so")
 
@@ -102,6 +104,9 @@ _SIGS = {
     "dw_greedy_select_history": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                                  [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_float, C.c_int, C.c_void_p], C.c_int),
+    "dw_greedy_select_bias": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                              [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
     "dw_sample_select": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
                          [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                           C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
@@ -667,6 +672,29 @@ class HipOps:
             int(begin_index), int(eos), int(fill), _p(done), _p(cur), float(repetition_penalty), int(no_repeat_ngram),
             self._stream()), "greedy_select_history")
 
+    # SEL_BIAS_S of csrc/select_rules.h (dw_greedy_select_bias refuses more); the cap on a sequence's length is the host's
+    BIAS_MAX_SEQUENCES, BIAS_MAX_TOKENS = SEQUENCE_BIAS_MAX_SEQUENCES, SEQUENCE_BIAS_MAX_TOKENS
+
+    def greedy_select_bias(self, logits, V, tokens, n, cur, *, suppress=None, begin_suppress=None, first=False, no_eos=False,
+                           forced=False, ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, fill=-1, done=None,
+                           repetition_penalty=1.0, no_repeat_ngram=0, bias_tok=None, bias_off=None, bias_val=None):
+        """`greedy_select_history` with the table of `sequence_bias` / `bad_words_ids` (decoding.sequence_bias_table: tok int32
+        [T], off int32 [S + 1], val f32 [S], ordered by the column of each sequence's last token) applied in front, in the same
+        single launch.  Without a table (S = 0) it selects what `greedy_select_history` selects."""
+        B = tokens.shape[0]
+        self._check_select(None if forced else logits, B, V, suppress, begin_suppress, tokens, cur, done)
+        S = 0 if bias_off is None else bias_off.numel() - 1
+        if S > 0:
+            assert S <= self.BIAS_MAX_SEQUENCES and bias_val.numel() == S and 0 < bias_tok.numel() <= S * self.BIAS_MAX_TOKENS
+            assert bias_tok.dtype == torch.int32 and bias_off.dtype == torch.int32 and bias_val.dtype == torch.float32
+            assert bias_tok.is_contiguous() and bias_off.is_contiguous() and bias_val.is_contiguous()
+        self._chk(self.lib.dw_greedy_select_bias(
+            _p(logits), B, int(V), logits.stride(0) if logits is not None else 0, _p(suppress), _p(begin_suppress),
+            int(first), int(no_eos), int(forced), int(ts_begin), int(max_initial), _p(tokens), tokens.stride(0), int(n),
+            int(begin_index), int(eos), int(fill), _p(done), _p(cur), float(repetition_penalty), int(no_repeat_ngram),
+            _p(bias_tok) if S > 0 else None, _p(bias_off) if S > 0 else None, _p(bias_val) if S > 0 else None, max(S, 0),
+            self._stream()), "greedy_select_bias")
+
     def sample_select(self, logits, V, tokens, n, cur, noise, *, suppress=None, begin_suppress=None, first=False, no_eos=False,
                       ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, fill=-1, done=None, repetition_penalty=1.0,
                       no_repeat_ngram=0, temperature=1.0, top_k=0, top_p=1.0):
@@ -921,6 +949,7 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("sumsq", "sumsq"), ("embed_fwd", "embed"), ("embed_bwd", "embed"), ("im2col_mel", "conv_aux"),
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),
                     ("pack_conv_weight", "conv_aux"), ("unpack_conv_grad", "conv_aux"), ("greedy_select", "select"), ("greedy_select_history", "select"),
+                    ("greedy_select_bias", "select"),
                     ("sample_select", "select"), ("beam_candidates", "beam"), ("beam_update", "beam"),
                     ("cross_attn_probs", "align"),
                     ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score"), ("dropout_fwd", "dropout_fwd"),

@@ -46,7 +46,7 @@ class PseudoLabeller:
     def __init__(self, model, feature_extractor, batch_size=16, max_new_tokens=255, prompt_ids=None, eos_token_id=None,
                  timestamp_rules=None, use_graphs=None, rank=0, world=1, suppress_tokens=None,
                  begin_suppress_tokens=None, num_beams=1, overlap=False, decode_cus=64, repetition_penalty=None,
-                 no_repeat_ngram_size=0):
+                 no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None):
         from .longform import history_soft
         self.model, self.fe = model, feature_extractor
         self.B, self.max_new = int(batch_size), int(max_new_tokens)
@@ -55,12 +55,15 @@ class PseudoLabeller:
         self._beam_kw = dict(suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens)
         # GenerationMixin's two rules against repetition loops: inside the selection kernel of the graph-captured token step
         # (decoding.GreedyDecoder `soft`) and of the seek loop's greedy passes; beam search does not take them
-        soft = history_soft(repetition_penalty, no_repeat_ngram_size)
+        # sequence_bias / bad_words_ids (hot-word boosts, forbidden words): the same launch, the same limits
+        soft = history_soft(repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, model.dims.vocab, eos_token_id)
         if soft is not None and self.num_beams > 1:
-            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size with num_beams > 1 are not implemented on the "
-                                      "MI355X path (greedy decoding only)")
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids with num_beams > 1 "
+                                      "are not implemented on the MI355X path (greedy decoding only)")
         self._history_kw = {} if soft is None else dict(repetition_penalty=soft["repetition_penalty"],
                                                         no_repeat_ngram_size=soft["no_repeat_ngram_size"])
+        if soft is not None and soft.get("sequence_bias") is not None:
+            self._history_kw["sequence_bias"] = soft["sequence_bias"]
         d = model.dims
         dev = model.ops.device
         self.dev = dev

@@ -290,6 +290,21 @@ int dw_greedy_select_history(const void* logits, int B, int V, int64_t ld, const
                              const uint8_t* begin_suppress, int first, int no_eos, int forced, int ts_begin, int max_initial,
                              int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, int fill, uint8_t* done,
                              int64_t* cur, float repetition_penalty, int no_repeat_ngram, void* stream);
+/* dw_greedy_select_history with GenerationMixin's SequenceBiasLogitsProcessor and NoBadWordsLogitsProcessor
+ * (`generate(sequence_bias=, bad_words_ids=)`) in the same launch.  The table holds S <= 1024 sequences of 1..32 token ids in
+ * [0, V): sequence s is bias_tok[bias_off[s], bias_off[s + 1]) (int32, device memory) with the bias bias_val[s] (f32; -inf =
+ * a bad word) for the column of its last token.  The entries must be ordered by that column, ascending; within a column their
+ * order is the order in which their biases are summed.  A one-token sequence always counts; a longer one is ignored when it is
+ * longer than the history (bias_off[s + 1] - bias_off[s] > n) and counts otherwise iff the last len - 1 tokens of
+ * tokens[b][0, n) equal its prefix.  The biases that count for a column are summed first (fp32, table order; no atomics on
+ * floats) and the sum is added to the logit once, in front of the repetition penalty; a column whose sum is -inf is never
+ * selected.  S = 0 (the pointers may be NULL) selects what dw_greedy_select_history selects.  The contents of the table are
+ * not checked (decoding.sequence_bias_table builds and validates it). */
+int dw_greedy_select_bias(const void* logits, int B, int V, int64_t ld, const uint8_t* suppress,
+                          const uint8_t* begin_suppress, int first, int no_eos, int forced, int ts_begin, int max_initial,
+                          int64_t* tokens, int64_t tok_ld, int n, int begin_index, int eos, int fill, uint8_t* done,
+                          int64_t* cur, float repetition_penalty, int no_repeat_ngram, const int* bias_tok,
+                          const int* bias_off, const float* bias_val, int S, void* stream);
 /* The sampled step (`generate(do_sample=True, temperature=, top_k=, top_p=)`: TF:generation/utils.py `_get_logits_processor` +
  * `_sample`; the fallback passes of TF:generation_whisper.py `generate_with_fallback`, run_eval.py:690-739) in one launch.  The
  * processed score of every column is the one dw_greedy_select_history judges (excluded = -inf); then, in the reference's order,
