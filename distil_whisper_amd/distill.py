@@ -238,7 +238,8 @@ class DistillationTrainer:
                  lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, freeze_encoder=False,
                  share_encoder=False, freeze_embed_positions=False, process_group=None, mel_filters=None,
                  overlap_teacher=False, overlap_wgrad=False, pad_teacher_rows=False, bucket_bytes=256 << 20,
-                 always_reduce=False, comm_watchdog_s=0.0, dropout=None, activation_dropout=None, dropout_seed=0):
+                 always_reduce=False, comm_watchdog_s=0.0, dropout=None, activation_dropout=None, dropout_seed=0,
+                 spec_augment=None, augment_teacher=True):
         self.ops = ops
         self.sdims, self.tdims = WhisperDims.from_any(student_dims), WhisperDims.from_any(teacher_dims)
         frozen = []
@@ -261,6 +262,23 @@ class DistillationTrainer:
                                         if activation_dropout is None else activation_dropout)
         self.dropout_seed = int(dropout_seed) + rank
         self.student.set_dropout(self.dropout, self.activation_dropout, seed=self.dropout_seed)
+        # SpecAugment of the student's training forward (spec_augment.py): `spec_augment` is a dict of the six `mask_*` parameters
+        # (default: the student config's fields when its `apply_spec_augment` is true).  The features are masked ONCE per student
+        # forward into a buffer of the trainer's own -- the caller's tensor is never written (the teacher may be reading it on the
+        # side stream, and a captured step needs a static address).  augment_teacher=True: the teacher reads the masked features
+        # too, as in the reference's loop, where the student's in-place masking is what `teacher_model(**batch)` then sees;
+        # False: the teacher reads the clean features.  Seed and step counter are dropout's.
+        from . import spec_augment as sa
+        sa_params = sa.params_from_config(student_dims) if spec_augment is None else sa.normalise(spec_augment)
+        self.spec_augment = sa_params if sa.active(sa_params) else None
+        self.augment_teacher = bool(augment_teacher)
+        if self.spec_augment is not None:
+            sa.validate(self.spec_augment, self.sdims.n_mels, 2 * self.sdims.max_src)
+            if share_encoder and not self.augment_teacher:
+                raise ValueError("augment_teacher=False with share_encoder: the teacher decodes on the student's encoder output, "
+                                 "which is that of the masked features")
+        self.student.set_spec_augment(self.spec_augment, seed=self.dropout_seed)
+        self._aug_buf = None
         self.temperature, self.kl_weight = temperature, kl_weight
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
@@ -330,12 +348,23 @@ class DistillationTrainer:
             labels_flat = labels_flat.index_select(0, live.idx)      # labels of the packed rows
         if self.overlap_teacher and self._tstream is None:
             self._tstream = torch.cuda.Stream(device=self.student_store.P.device)
+        feats_s = feats_t = input_features
+        ticked = False
+        if self.spec_augment is not None:
+            # (before the teacher is started: with augment_teacher it reads the masked features)
+            if self._aug_buf is None or self._aug_buf.shape != input_features.shape or self._aug_buf.device != input_features.device:
+                self._aug_buf = torch.empty_like(input_features)
+            S.dropout_tick()
+            ticked = True
+            feats_s = S.spec_augment(input_features, out=self._aug_buf)
+            if self.augment_teacher:
+                feats_t = feats_s
         side = self._tstream if (self.overlap_teacher and not self.share_encoder) else None
         if side is not None:
             main = torch.cuda.current_stream(input_features.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                enc_t, _ = T.encode(input_features, save=False)
+                enc_t, _ = T.encode(feats_t, save=False)
                 logits_t, _ = T.decode(decoder_input_ids, enc_t, save=False, live=live)
                 del enc_t
             # (no record_stream: the inputs are the caller's and stay alive over the call, the side stream is joined
@@ -343,8 +372,9 @@ class DistillationTrainer:
             # following step, which starts with side.wait_stream(main), i.e. after the loss kernel that reads it)
         S.training = True
         try:
-            S.dropout_tick()      # one per student forward, on the device: a captured step replays it (no launch with dropout off)
-            enc_s, ectx = S.encode(input_features, save=not self.freeze_encoder)
+            if not ticked:
+                S.dropout_tick()  # one per student forward, on the device: a captured step replays it (no launch with dropout off)
+            enc_s, ectx = S.encode(feats_s, save=not self.freeze_encoder)
             logits_s, dctx = S.decode(decoder_input_ids, enc_s, save=True, live=live)
         finally:
             S.training = False
@@ -354,7 +384,7 @@ class DistillationTrainer:
             t_ids = shift_tokens_right(labels, self.tdims.pad_token_id, self.tdims.decoder_start_token_id)
             logits_t, _ = T.decode(t_ids, enc_s, save=False, live=live)
         else:
-            enc_t, _ = T.encode(input_features, save=False)
+            enc_t, _ = T.encode(feats_t, save=False)
             logits_t, _ = T.decode(decoder_input_ids, enc_t, save=False, live=live)
             del enc_t
         R = B * Td if live is None else live.n
@@ -496,7 +526,8 @@ class DistillationTrainer:
         in_key = (tuple(inputs.shape), inputs.dtype, tuple(decoder_input_ids.shape), self.overlap_teacher,
                   self.student.wgrad_stream is not None,
                   # (a captured plan has these baked into its launches)
-                  self.temperature, self.kl_weight, self.max_grad_norm, self.eps, self.weight_decay, self._accum)
+                  self.temperature, self.kl_weight, self.max_grad_norm, self.eps, self.weight_decay, self._accum,
+                  None if self.spec_augment is None else tuple(sorted(self.spec_augment.items())), self.augment_teacher)
         key = in_key + (Te, Rc)
         ins = self._graph_inputs
         if ins is None or ins["key"] != in_key:
@@ -607,9 +638,12 @@ class DistillationTrainer:
                  "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                            "max_grad_norm": self.max_grad_norm, "temperature": self.temperature,
                            "kl_weight": self.kl_weight}}
-        if self.dropout or self.activation_dropout:       # a resumed run continues the mask sequence
+        if self.dropout or self.activation_dropout or self.spec_augment is not None:    # a resumed run continues the mask sequence
             state["dropout"] = {"dropout": self.dropout, "activation_dropout": self.activation_dropout,
                                 "seed": self.dropout_seed, "step": int(self.student.drop_state.item())}
+            if self.spec_augment is not None:
+                state["dropout"]["spec_augment"] = dict(self.spec_augment)
+                state["dropout"]["augment_teacher"] = self.augment_teacher
         return state
 
     def load_state_dict(self, state):
@@ -633,4 +667,8 @@ class DistillationTrainer:
             self.dropout, self.activation_dropout = float(dr["dropout"]), float(dr["activation_dropout"])
             self.dropout_seed = int(dr["seed"])
             self.student.set_dropout(self.dropout, self.activation_dropout, seed=self.dropout_seed, step=int(dr["step"]))
+            if dr.get("spec_augment") is not None:
+                self.spec_augment = dict(dr["spec_augment"])
+                self.augment_teacher = bool(dr.get("augment_teacher", True))
+            self.student.set_spec_augment(self.spec_augment, seed=self.dropout_seed, step=int(dr["step"]))
         self.drop_graph()         # (a captured step has the old hyper-parameters baked in: re-planned on next use)

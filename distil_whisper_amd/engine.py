@@ -321,6 +321,7 @@ class WhisperEngine:
         self.p_drop = self.p_act = 0.0
         self.drop_seed, self.drop_state = 0, None
         self.keep_masks = None      # tests: a dict that receives {site: mask buffer} of the last training forward
+        self.spec = None            # SpecAugment (set_spec_augment): the six mask parameters, or None = off
 
     # ---- dropout -------------------------------------------------------------------------------------------------
     # `dropout` (embeddings, the three residual branches) and `activation_dropout` (GELU output of fc1) of TF:modeling_whisper.py:
@@ -344,12 +345,50 @@ class WhisperEngine:
         if self.p_drop or self.p_act:
             if not hasattr(self.ops, "dropout_fwd"):
                 raise RuntimeError(f"ops '{getattr(self.ops, 'name', self.ops)}' has no dropout kernels")
-            self.drop_state = self.ops.dropout_state(step)
+            self.drop_state = self._new_drop_state(step)
+
+    def _new_drop_state(self, step):
+        # (ops without the dropout kernels -- the torch oracle under SpecAugment alone -- keep the counter as a plain tensor)
+        if hasattr(self.ops, "dropout_state"):
+            return self.ops.dropout_state(step)
+        return torch.tensor([int(step)], dtype=torch.int64, device=self.ops.device)
 
     def dropout_tick(self):
         """Once per training forward (before it): the next forward draws the masks of the next step."""
-        if self.p_drop or self.p_act:
-            self.ops.dropout_tick(self.drop_state)
+        if self.p_drop or self.p_act or self.spec is not None:
+            if hasattr(self.ops, "dropout_tick"):
+                self.ops.dropout_tick(self.drop_state)
+            else:
+                self.drop_state += 1
+
+    # ---- SpecAugment ---------------------------------------------------------------------------------------------
+    # `apply_spec_augment` / `mask_time_*` / `mask_feature_*` of TF:modeling_whisper.py WhisperModel._mask_input_features: spans
+    # of the input features are zeroed in front of the encoder.  The draws share dropout's generator, seed and step counter at two
+    # sites of their own (include/dwamd.h dw_spec_augment), so dropout's masks are the same with and without it.
+    def set_spec_augment(self, params, seed=None, step=None):
+        """params: the six mask parameters (spec_augment.normalise) or None = off; seed / step: as set_dropout (None keeps them)."""
+        from .spec_augment import active, normalise
+        params = None if params is None else normalise(params)
+        self.spec = params if active(params) else None
+        if seed is not None:
+            self.drop_seed = int(seed)
+        if self.spec is not None and (self.drop_state is None or step is not None):
+            self.drop_state = self._new_drop_state(step or 0)
+
+    def spec_augment(self, x, lengths=None, out=None):
+        """Mask fp32 features x [B, n_mels, T] with the draws of the current step: in place, or into `out`.  The HIP kernel where
+        the ops object has it, else the torch statement of the same draws."""
+        from . import spec_augment as sa
+        want = self.keep_masks is not None
+        if hasattr(self.ops, "spec_augment"):
+            out, tm, fm = self.ops.spec_augment(x, self.drop_seed, self.drop_state, self.spec, lengths=lengths, out=out,
+                                                want_masks=want)
+        else:
+            out, tm, fm = sa.spec_augment_torch(x, self.drop_seed, self.drop_state, self.spec, lengths=lengths, out=out,
+                                                want_masks=want)
+        if want:
+            self.keep_masks[sa.SITE_TIME], self.keep_masks[sa.SITE_FEATURE] = tm, fm
+        return out
 
     def _drop(self, save):
         on = save and self.training

@@ -255,7 +255,12 @@ class _Model(nn.Module):
 
 def check_regularisers(config):
     """`dropout` and `activation_dropout` (the row-local dropouts: embeddings, the three residual branches, the GELU output of
-    fc1) are built and apply in training mode; the other regularisers of `transformers.WhisperConfig` are not."""
+    fc1) and SpecAugment (`apply_spec_augment`, spec_augment.py) are built and apply in training mode; the other regularisers
+    of `transformers.WhisperConfig` are not."""
+    from .spec_augment import params_from_config, validate
+    sa = params_from_config(config)
+    if sa is not None:      # the reference's messages, at construction instead of the first training forward
+        validate(sa, int(getattr(config, "num_mel_bins", 80)), 2 * int(getattr(config, "max_source_positions", 1500)))
     for k in ("dropout", "activation_dropout"):
         v = getattr(config, k, 0.0) or 0.0
         if not 0.0 <= float(v) < 1.0:
@@ -280,7 +285,9 @@ class WhisperConfig:
                      eos_token_id=50256, decoder_start_token_id=50257, activation_function="gelu", dropout=0.0,
                      attention_dropout=0.0, activation_dropout=0.0, encoder_layerdrop=0.0, decoder_layerdrop=0.0,
                      scale_embedding=False, use_cache=True, suppress_tokens=None, begin_suppress_tokens=None,
-                     max_length=448, forced_decoder_ids=None)
+                     max_length=448, forced_decoder_ids=None, apply_spec_augment=False, mask_time_prob=0.05,
+                     mask_time_length=10, mask_time_min_masks=2, mask_feature_prob=0.0, mask_feature_length=10,
+                     mask_feature_min_masks=0)
 
     def __init__(self, **kw):
         for k, v in self._DEFAULTS.items():
@@ -430,8 +437,19 @@ class _EngineFn(torch.autograd.Function):
         enc_train = train and model._encoder_requires_grad()
         ectx = None
         eng.training = bool(train and model.training)
-        if eng.training:
-            eng.dropout_tick()          # this forward draws the masks of the next step (nothing happens with both probabilities 0)
+        # SpecAugment masks on the module's training flag alone, in front of the encoder (so not when `encoder_outputs` came
+        # in), and in place on the caller's tensor -- TF:modeling_whisper.py WhisperModel.forward / _mask_input_features
+        augment = bool(model.training and eng.spec is not None and enc_in is None)
+        lengths, model._spec_lengths = model._spec_lengths, None
+        if eng.training or augment:
+            eng.dropout_tick()          # this forward draws the masks of the next step (nothing happens with everything off)
+        if augment:
+            if input_features.dtype == torch.float32 and input_features.is_contiguous():
+                eng.spec_augment(input_features, lengths=lengths)
+            else:
+                masked = eng.spec_augment(input_features.to(torch.float32).contiguous(), lengths=lengths)
+                input_features.copy_(masked)
+                input_features = masked
         if enc_in is None:
             enc, ectx = eng.encode(input_features.to(torch.float32).contiguous(), save=enc_train)
         else:
@@ -585,6 +603,12 @@ class WhisperForConditionalGeneration(nn.Module):
         p_drop, p_act = float(getattr(config, "dropout", 0.0) or 0.0), float(getattr(config, "activation_dropout", 0.0) or 0.0)
         if not pure_bf16 and (p_drop or p_act):
             self.engine.set_dropout(p_drop, p_act, seed=dropout_seed)
+        # `config.apply_spec_augment`: training-mode forwards mask the input features in place (spec_augment.py); seed and step
+        # counter are dropout's
+        from .spec_augment import params_from_config
+        if not pure_bf16:
+            self.engine.set_spec_augment(params_from_config(config), seed=dropout_seed)
+        self._spec_lengths = None
         self._decoders = {}
         self.model = _Model(self.dims)
         self.proj_out = nn.Linear(self.dims.d_model, self.dims.vocab, bias=False, device="meta")
@@ -751,6 +775,9 @@ class WhisperForConditionalGeneration(nn.Module):
             raise ValueError(f"Whisper expects the mel input features to be of length {2 * d.max_src}, but found "
                              f"{input_features.shape[-1]}. Make sure to pad the input mel features to {2 * d.max_src}.")
         self._sync_shadow()
+        if attention_mask is not None and enc_in is None and self.training and self.engine.spec is not None:
+            from .spec_augment import lengths_from_attention_mask
+            self._spec_lengths = lengths_from_attention_mask(attention_mask)       # (on the device: no round trip)
         if valid_len is None and labels is not None and self.skip_dead_positions and labels.shape == decoder_input_ids.shape:
             sel = _PendingLens(labels)           # (resolved inside _EngineFn.forward, behind the encoder's launches)
             if sel.lens is not None:             # the other model already fetched them for this very tensor

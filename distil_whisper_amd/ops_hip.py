@@ -130,6 +130,8 @@ _SIGS = {
     "dw_dropout_bwd": ([C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float,
                         C.c_void_p], C.c_int),
     "dw_dropout_tick": ([C.c_void_p, C.c_void_p], C.c_int),
+    "dw_spec_augment": ([C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_double,
+                         C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "dw_score_tokens": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                          C.c_void_p, C.c_void_p], C.c_int),
@@ -911,6 +913,31 @@ class HipOps:
                                           1.0 / (1.0 - p), self._stream()), "dropout_bwd")
         return out
 
+    # ---- SpecAugment of the training forward (csrc/spec_augment.hip; TF:modeling_whisper.py _mask_input_features) ----------
+    def spec_augment(self, x, seed, state, params, lengths=None, out=None, want_masks=False):
+        """Zero the time / feature spans of fp32 features x [B, n_mels, T] drawn for the step in `state` (the device-resident
+        counter of dropout_state): in place (out None or x) or into `out`.  params: the six `mask_*` values
+        (spec_augment.normalise); lengths: int32 [B] valid frames per row on the device, or None.
+        -> (out, time mask uint8 [B, T], feature mask uint8 [B, n_mels]) (the masks None unless want_masks)."""
+        from .spec_augment import validate
+        assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+        B, n_mels, T = x.shape
+        validate(params, n_mels, T)
+        if out is None:
+            out = x
+        assert out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
+        assert state.dtype == torch.int64 and state.numel() == 1
+        assert lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()
+                                   and lengths.device == x.device)
+        tm = self.empty((B, T), torch.uint8) if want_masks else None
+        fm = self.empty((B, n_mels), torch.uint8) if want_masks else None
+        self._chk(self.lib.dw_spec_augment(_p(x), _p(out), B, n_mels, T, _p(lengths), float(params["mask_time_prob"]),
+                                           int(params["mask_time_length"]), int(params["mask_time_min_masks"]),
+                                           float(params["mask_feature_prob"]), int(params["mask_feature_length"]),
+                                           int(params["mask_feature_min_masks"]), int(seed) & (2**64 - 1), _p(state), _p(tm),
+                                           _p(fm), self._stream()), "spec_augment")
+        return out, tm, fm
+
     def adamw(self, p, g, m, v, shadow, sumsq, max_norm, grad_mul, lr, beta1, beta2, eps, weight_decay, step):
         assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
         self._chk(self.lib.dw_adamw(_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), _p(sumsq), float(max_norm),
@@ -953,5 +980,5 @@ for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("
                     ("sample_select", "select"), ("beam_candidates", "beam"), ("beam_update", "beam"),
                     ("cross_attn_probs", "align"),
                     ("align_prepare", "align"), ("dtw", "align"), ("score_tokens", "score"), ("dropout_fwd", "dropout_fwd"),
-                    ("dropout_bwd", "dropout_bwd")):
+                    ("dropout_bwd", "dropout_bwd"), ("spec_augment", "spec_augment")):
     setattr(HipOps, _name, _timed(_key)(getattr(HipOps, _name)))

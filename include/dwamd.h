@@ -267,6 +267,32 @@ int dw_dropout_bwd(const void* dy, int dy_dtype, int64_t lddy, const uint8_t* ma
                    int rows, int cols, float scale, void* stream);
 int dw_dropout_tick(uint64_t* step, void* stream);
 
+/* ---- a10c: SpecAugment of the training forward ------------------------------------------------------------------
+ * TF:modeling_whisper.py _compute_mask_indices / WhisperModel._mask_input_features (`apply_spec_augment`, `mask_time_*`,
+ * `mask_feature_*`): spans of `mask_length` positions are zeroed along the time axis (features[b, :, t]) and / or the
+ * feature axis (features[b, f, :]) of the fp32 log-mel features [B][n_mels][T].  ONE launch draws both masks of every row
+ * and applies them; out == in is the in-place form (only the zeros are stored), otherwise out = masked copy of in.
+ * An axis with mask_*_prob <= 0 is not masked (and its length is not checked).  Per axis (time: axis_len = T, len_b =
+ * lengths[b] clamped to [0, T], or T when lengths is NULL; feature: axis_len = len_b = n_mels), in double precision:
+ *   epsilon = word 0 of Philox4x32-10(counter = (0, site, step_lo, step_hi), key = seed) * 2^-32, one per axis and call;
+ *   n(len)  = (int)(prob * len / mask_length + epsilon); = max(n, min_masks); = axis_len / mask_length if n * mask_length >
+ *             axis_len; = max(len - (mask_length - 1), 0) if that is smaller;  n_b = n(len_b), max_n = n(axis_len);
+ *   max_n == 0: no position of any row is masked.  n_b == 0 < max_n: position axis_len - 1 of row b alone is masked (the
+ *   reference's dummy index).  Otherwise n_b distinct starts are drawn from [0, M), M = len_b - (mask_length - 1), by Floyd's
+ *   subset algorithm: for w = 0 .. n_b - 1, j = M - n_b + w, t = (r_w * (j + 1)) >> 32, take j if t was taken before, where
+ *   r_w is word (w & 3) of Philox4x32-10(counter = (((b + 1) << 16) | (w >> 2), site, step_lo, step_hi), key = seed); the
+ *   mask is the union of [start, start + mask_length).
+ * site = DW_SPEC_SITE_TIME / DW_SPEC_SITE_FEATURE, above every site of dw_dropout_fwd (< 512), so dropout's masks do not
+ * depend on SpecAugment; `step` is dropout's device-resident counter (dw_dropout_tick).  time_mask uint8 [B][T] and feat_mask
+ * uint8 [B][n_mels] (1 = zeroed) are written when not NULL.  DW_EINVAL: null in / out / step, mask_length < 1 or > axis_len
+ * of an active axis; DW_EUNSUP: B > 65534, T or n_mels > 16384. */
+#define DW_SPEC_SITE_TIME 512u
+#define DW_SPEC_SITE_FEATURE 513u
+int dw_spec_augment(const float* in, float* out, int B, int n_mels, int T, const int32_t* lengths, double mask_time_prob,
+                    int mask_time_length, int mask_time_min_masks, double mask_feature_prob, int mask_feature_length,
+                    int mask_feature_min_masks, uint64_t seed, const uint64_t* step, uint8_t* time_mask, uint8_t* feat_mask,
+                    void* stream);
+
 /* ---- a11: token selection of one greedy-decoding step for the whole batch (TF:generation/logits_process.py processors
  * MinNewTokensLength, SuppressTokensAtBegin, SuppressTokens, WhisperTimeStamp as installed by
  * TF:models/whisper/generation_whisper.py:1774-1812, then argmax and the EOS / pad bookkeeping of GenerationMixin).
