@@ -766,12 +766,210 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16* qkv, bf16* c
     *(bf16x8*)(cache + ((b * max_len + t + j) * 2L * D) + c) = *(const bf16x8*)(qkv + row * 3L * D + D + c);
 }
 
-extern "C" int dw_decode_step(const DwDecodeStep* d, void* stream) {
-    DW_CLEAR_ERR();
-    if (!d || !d->ids || !d->tok_emb || !d->pos_emb || !d->layers || !d->lm_head || !d->x || !d->h || !d->qkv || !d->o ||
-        !d->a || !d->logits)
-        return DW_EINVAL;
-    const int B = d->batch, n = d->n_new, D = d->d_model, H = d->heads, F = d->ffn, t = d->t;
+// ---------------------------------------------------------------------------------------------------------------------
+// The cached pass at per-row positions (dw_decode_step_rows; the verify / catch-up / draft passes of speculative decoding with
+// per-row acceptance, decoding._assisted_rounds_device_rows).  Row b of the batch stands at position row_t[b]: its n new tokens
+// take the position embeddings row_t[b] + j, their K/V go to cache rows row_t[b] + j and query j sees the keys [0, row_t[b] + j].
+// row_t is device memory that only these three kernels read; each clamps it to [0, max_t], the host's bound that the caller
+// checked against the cache (max_t + n <= max_len): a stale or wild entry cannot reach past a row's own cache.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int row_pos(const int32_t* row_t, long b, int max_t) { return min(max(row_t[b], 0), max_t); }
+
+// embed_fwd_kernel (elementwise.hip) with the position row taken per sequence: x[b * n + j] = tok[ids[b][j]] + pos[row_t[b] + j],
+// the sum in fp32, rounded once where the stream is bf16.  BF: tables and stream bf16, else both f32 (DwDecodeStep.stream_dtype).
+template <bool BF>
+__global__ __launch_bounds__(256) void embed_rows_kernel(const int64_t* ids, const void* tok, const void* pos, void* out,
+                                                         const int32_t* row_t, int max_t, int n, int D, long nvec) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvec) return;
+    const int dv = D >> 2;
+    const long row = i / dv;
+    const int c = (int)(i - row * dv) * 4;
+    const long b = row / n;
+    const long t = row_pos(row_t, b, max_t) + (int)(row - b * n);
+    const long id = ids[row];
+    if (BF) {
+        const bf16x4 x = *(const bf16x4*)((const bf16*)tok + id * D + c);
+        const bf16x4 y = *(const bf16x4*)((const bf16*)pos + t * D + c);
+        bf16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = f2bf(bf2f(x[e]) + bf2f(y[e]));
+        *(bf16x4*)((bf16*)out + row * D + c) = o;
+    } else {
+        const f32x4 a = *(const f32x4*)((const float*)tok + id * D + c);
+        const f32x4 p = *(const f32x4*)((const float*)pos + t * D + c);
+        *(f32x4*)((float*)out + row * D + c) = a + p;
+    }
+}
+
+// kv_append_kernel with the first cache row taken per sequence: cache[b][row_t[b] + j][0 .. 2D) = qkv[b * n + j][D .. 3D)
+__global__ __launch_bounds__(256) void kv_append_rows_kernel(const bf16* qkv, bf16* cache, const int32_t* row_t, int max_t,
+                                                              int n_new, int max_len, int D, long nvec) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvec) return;
+    const int per_row = (2 * D) >> 3;
+    const long row = i / per_row;
+    const int c = (int)(i - row * per_row) << 3;
+    const long b = row / n_new;
+    const int j = (int)(row - b * n_new);
+    const long t = row_pos(row_t, b, max_t);
+    *(bf16x8*)(cache + ((b * max_len + t + j) * 2L * D) + c) = *(const bf16x8*)(qkv + row * 3L * D + D + c);
+}
+
+// Cached self-attention of a few queries against a per-row key count: n <= AR_MAXQ queries of head h of sequence b (rows b * n + j
+// of qkv, head_dim 64) over the sequence's cache rows [0, t0 + n), t0 = row_t[b]; query j sees the keys k <= t0 + j.  One
+// workgroup of four waves per (head, sequence); the work is a few hundred keys, so the kernel is three short phases over LDS
+// instead of tiles:
+//   1. scores: eight lanes share a key (16 bytes = 8 head dimensions each, AR_UN key groups requested ahead), every query's dot
+//      product against it from the fp32 q in LDS (bf16 q x scale x log2 e), s[j][k] to LDS;
+//   2. softmax: wave w owns the queries j = w (mod 4): the maximum and the sum over the keys the query sees, P rounded to bf16 (as
+//      the other attention kernels feed their PV product) back into LDS, a key behind the query's own position as 0;
+//   3. PV: the same lane-to-key mapping over V, AR_JC queries per sweep in registers (8 dimensions x AR_JC accumulators), summed
+//      over the key slots of a wave by shuffles and over the waves through LDS, divided by the sum, stored as bf16.
+// Same arithmetic as attn_decode_proj_kernel above (fp32 dot products of bf16 operands, exp2, unrounded sum, rounded P); the order
+// of the sums over the keys is this kernel's own.  LDS: n x 64 q + n x ldk scores + 4 x AR_JC x 64 partial outputs + n sums, ldk
+// = max_t + n rounded up to 4 (attn_rows_smem; the caller refuses more than 64 KiB).
+constexpr int AR_NT = 256, AR_NW = AR_NT / 64, AR_JC = 8, AR_UN = 4, AR_MAXQ = 32;
+static size_t attn_rows_smem(int n, int ldk) { return ((size_t)n * 64 + (size_t)n * ldk + AR_NW * AR_JC * 64 + AR_MAXQ) * 4; }
+
+__global__ __launch_bounds__(AR_NT) void attn_rows_kernel(const bf16* qkv, long ldq, const bf16* cache, long ldkv, long kv_rows,
+                                                          const int32_t* row_t, int max_t, bf16* o, long ldo, int n, int ldk,
+                                                          float scale) {
+    extern __shared__ __attribute__((aligned(16))) float arsm[];
+    float* qs = arsm;                                   // [n][64]
+    float* sc = qs + n * 64;                            // [n][ldk]
+    float* part = sc + (long)n * ldk;                   // [AR_NW][AR_JC][64]
+    float* lsum = part + AR_NW * AR_JC * 64;            // [n]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = blockIdx.x, b = blockIdx.y;
+    const int t0 = __builtin_amdgcn_readfirstlane(row_pos(row_t, b, max_t));
+    const int Lk = t0 + n;                              // keys of the last query; <= max_t + n <= ldk
+    const float c = scale * 1.4426950408889634f;
+    if (tid < n * 8) {
+        const int j = tid >> 3, d0 = (tid & 7) * 8;
+        const bf16x8 q = *(const bf16x8*)(qkv + ((long)b * n + j) * ldq + h * 64 + d0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qs[j * 64 + d0 + e] = bf2f(q[e]) * c;
+    }
+    __syncthreads();
+    // ---- 1. scores ----
+    const int sub = tid >> 3, ds = (tid & 7) * 8;       // key slot 0..31 of a sweep, head dimensions ds .. ds + 7
+    const bf16* K = cache + (long)b * kv_rows * ldkv + h * 64 + ds;
+    const bf16* V = K + (ldkv >> 1);                    // (K | V per cache row: V starts D = ldkv / 2 columns in)
+    for (int k0 = 0; k0 < Lk; k0 += 32 * AR_UN) {
+        bf16x8 kr[AR_UN];
+#pragma unroll
+        for (int u = 0; u < AR_UN; ++u) {
+            const int k = min(k0 + u * 32 + sub, Lk - 1);
+            kr[u] = *(const bf16x8*)(K + (long)k * ldkv);
+        }
+#pragma unroll
+        for (int u = 0; u < AR_UN; ++u) {
+            const int k = k0 + u * 32 + sub;
+            float kf[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kf[e] = bf2f(kr[u][e]);
+            for (int j = 0; j < n; ++j) {
+                const f32x4 qa = *(const f32x4*)(qs + j * 64 + ds), qb = *(const f32x4*)(qs + j * 64 + ds + 4);
+                float s = 0.f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s = fmaf(qa[e], kf[e], s);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s = fmaf(qb[e], kf[4 + e], s);
+                s += __shfl_xor(s, 1);
+                s += __shfl_xor(s, 2);
+                s += __shfl_xor(s, 4);
+                if ((tid & 7) == 0 && k < Lk) sc[(long)j * ldk + k] = s;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 2. softmax of query j over its t0 + j + 1 keys ----
+    for (int j = wave; j < n; j += AR_NW) {
+        float* row = sc + (long)j * ldk;
+        const int nk = t0 + j + 1;
+        float mx = NEG_BIG_D;
+        for (int k = lane; k < nk; k += 64) mx = fmaxf(mx, row[k]);
+        mx = wave_max(mx);
+        float sum = 0.f;
+        for (int k = lane; k < Lk; k += 64) {
+            float p = 0.f;
+            if (k < nk) {
+                p = __builtin_amdgcn_exp2f(row[k] - mx);
+                sum += p;
+                p = round_bf16(p);
+            }
+            row[k] = p;
+        }
+        sum = wave_sum(sum);
+        if (lane == 0) lsum[j] = sum;
+    }
+    __syncthreads();
+    // ---- 3. PV, AR_JC queries per sweep over the keys ----
+    for (int j0 = 0; j0 < n; j0 += AR_JC) {
+        const int nj = min(AR_JC, n - j0);
+        const int Lj = t0 + j0 + nj;                    // keys of the sweep's last query
+        float acc[AR_JC][8];
+#pragma unroll
+        for (int jj = 0; jj < AR_JC; ++jj)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[jj][e] = 0.f;
+        for (int k0 = 0; k0 < Lj; k0 += 32 * AR_UN) {
+            bf16x8 vr[AR_UN];
+#pragma unroll
+            for (int u = 0; u < AR_UN; ++u) {
+                const int k = min(k0 + u * 32 + sub, Lj - 1);
+                vr[u] = *(const bf16x8*)(V + (long)k * ldkv);
+            }
+#pragma unroll
+            for (int u = 0; u < AR_UN; ++u) {
+                const int k = k0 + u * 32 + sub;
+                if (k < Lj) {
+                    float vf[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) vf[e] = bf2f(vr[u][e]);
+#pragma unroll
+                    for (int jj = 0; jj < AR_JC; ++jj) {
+                        if (jj < nj) {
+                            const float p = sc[(long)(j0 + jj) * ldk + k];
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) acc[jj][e] = fmaf(p, vf[e], acc[jj][e]);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int jj = 0; jj < AR_JC; ++jj) {
+            if (jj < nj) {                              // (uniform: every lane of the wave takes part in the shuffles)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float a = acc[jj][e];
+                    a += __shfl_xor(a, 8);
+                    a += __shfl_xor(a, 16);
+                    a += __shfl_xor(a, 32);
+                    if (lane < 8) part[(wave * AR_JC + jj) * 64 + ds + e] = a;
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < nj * 64; i += AR_NT) {
+            const int jj = i >> 6, dcol = i & 63;
+            float a = 0.f;
+#pragma unroll
+            for (int w = 0; w < AR_NW; ++w) a += part[(w * AR_JC + jj) * 64 + dcol];
+            o[((long)b * n + j0 + jj) * ldo + h * 64 + dcol] = f2bf(a / lsum[j0 + jj]);
+        }
+        __syncthreads();
+    }
+}
+
+// The pass of dw_decode_step (row_t == nullptr: every row starts at d->t) and of dw_decode_step_rows (row b starts at row_t[b] <=
+// max_t, a device array the host never reads: `t` is then max_t and sizes launches only).  The rows pass swaps three launches --
+// embedding, K/V append, self-attention (the *_rows kernels above) -- and keeps every other launch of the uniform pass.
+static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void* stream) {
+    const int B = d->batch, n = d->n_new, D = d->d_model, H = d->heads, F = d->ffn;
     if (B <= 0 || n <= 0 || D != H * 64 || (D & 63) || (F & 63) || d->n_layers <= 0 || d->src_len <= 0 || t < 0 ||
         t + n > d->max_len || d->ldv < d->vocab || (d->ldv & 15))
         return DW_EINVAL;
@@ -779,16 +977,41 @@ extern "C" int dw_decode_step(const DwDecodeStep* d, void* stream) {
     const int rows = B * n;
     const long ldx = d->cross_kv_ld > 0 ? d->cross_kv_ld : 2L * D;        // row pitch of the cross-attention K | V
     if (ldx < 2L * D || (ldx & 7)) return DW_EINVAL;
+    const int ldk = (t + n + 3) & ~3;                                     // rows pass: pitch of a query's scores in LDS
+    const size_t rows_smem = attn_rows_smem(n, ldk);
+    if (row_t) {                                                          // (refused before anything is launched)
+        if (n > AR_MAXQ || B > 65535 || rows_smem > 65536) return DW_EUNSUP;
+        for (int l = 0; l < d->n_layers; ++l) {
+            const DwDecoderLayer& L = d->layers[l];
+            if (!L.wqkv || !L.wo || !L.wq || !L.wo2 || !L.w1 || !L.w2 || !L.self_kv || !L.cross_kv) return DW_EINVAL;
+        }
+    }
     const size_t es = d->stream_dtype == DW_F32 ? 4 : 2;
-    int rc = dw_embed_fwd(d->ids, d->tok_emb, (const char*)d->pos_emb + (size_t)t * D * es, d->stream_dtype, d->x,
+    int rc = DW_OK;
+    if (row_t) {
+        const long nvec = (long)rows * (D >> 2);
+        const dim3 grid((nvec + 255) / 256), block(256);
+        if (d->stream_dtype == DW_BF16)
+            hipLaunchKernelGGL(embed_rows_kernel<true>, grid, block, 0, (hipStream_t)stream, (const int64_t*)d->ids, d->tok_emb,
+                               d->pos_emb, d->x, row_t, t, n, D, nvec);
+        else
+            hipLaunchKernelGGL(embed_rows_kernel<false>, grid, block, 0, (hipStream_t)stream, (const int64_t*)d->ids, d->tok_emb,
+                               d->pos_emb, d->x, row_t, t, n, D, nvec);
+        DW_CHECK_LAUNCH();
+    } else {
+        rc = dw_embed_fwd(d->ids, d->tok_emb, (const char*)d->pos_emb + (size_t)t * D * es, d->stream_dtype, d->x,
                           d->stream_dtype, B, n, D, stream);
+    }
     if (rc != DW_OK) return rc;
     // With few rows the LayerNorm in front of a projection is computed inside the weight-streaming GEMM and the new
     // K/V go straight into the cache (DwGemm.ln_x / kv_out): 9 launches per layer instead of 13.
-    const bool fuse_ln = rows <= 32 && D <= 1280 && !(g_decode_fuse_off & 1), fuse_kv = rows <= 64 && !(g_decode_fuse_off & 2);
+    // (the rows pass takes neither fusion that bakes a uniform position: the GEMM's kv_out / kv_row0 and the self-attention with
+    // its projection inside)
+    const bool fuse_ln = rows <= 32 && D <= 1280 && !(g_decode_fuse_off & 1);
+    const bool fuse_kv = !row_t && rows <= 64 && !(g_decode_fuse_off & 2);
     // token step: the q (q / k / v) projection of a head is computed by the attention workgroup of that head
     const bool proj_ok = n == 1 && decode_proj_dim_ok(D);
-    const bool proj_self = proj_ok && !(g_decode_fuse_off & 4) && t + 1 <= 8192;
+    const bool proj_self = !row_t && proj_ok && !(g_decode_fuse_off & 4) && t + 1 <= 8192;
     const bool proj_cross = proj_ok && !(g_decode_fuse_off & 8) && d->src_len <= 8192;
     auto gemm = [&](const void* a, long lda, const void* w, const float* bias, int N, int K, void* c, long ldc, int c_dtype,
                     int act, const void* r, const float* ln_g, const float* ln_b, void* kv) -> int {
@@ -831,15 +1054,25 @@ extern "C" int dw_decode_step(const DwDecodeStep* d, void* stream) {
                       fuse_kv ? L.self_kv : nullptr);
         }
         if (rc != DW_OK) return rc;
+        const bf16* kc = (const bf16*)L.self_kv;
+        if (row_t) {
+            const long nvec = (long)rows * ((2 * D) >> 3);
+            hipLaunchKernelGGL(kv_append_rows_kernel, dim3((nvec + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                               (const bf16*)d->qkv, (bf16*)L.self_kv, row_t, t, n, d->max_len, D, nvec);
+            DW_CHECK_LAUNCH();
+            hipLaunchKernelGGL(attn_rows_kernel, dim3(H, B), dim3(AR_NT), rows_smem, (hipStream_t)stream, (const bf16*)d->qkv,
+                               3L * D, kc, 2L * D, (long)d->max_len, row_t, t, (bf16*)d->o, (long)D, n, ldk, 0.125f);
+            DW_CHECK_LAUNCH();
+        } else {
         if (!fuse_kv) {
             const long nvec = (long)rows * ((2 * D) >> 3);
             hipLaunchKernelGGL(kv_append_kernel, dim3((nvec + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                                (const bf16*)d->qkv, (bf16*)L.self_kv, n, t, d->max_len, D, nvec);
             DW_CHECK_LAUNCH();
         }
-        const bf16* kc = (const bf16*)L.self_kv;
         if ((rc = dw_attn_fwd_ex(d->qkv, kc, kc + D, d->o, nullptr, B, H, n, t + n, 3 * D, 2 * D, 2 * D, D, n, d->max_len,
                                  n > 1 ? 2 : 0, 0.125f, stream)) != DW_OK) return rc;
+        }
         }
         if ((rc = gemm(d->o, D, L.wo, L.bo, D, D, d->x, D, d->stream_dtype, 0, d->x, nullptr, nullptr, nullptr)) != DW_OK)
             return rc;
@@ -879,4 +1112,20 @@ extern "C" int dw_decode_step(const DwDecodeStep* d, void* stream) {
     if ((rc = dw_layernorm_fwd(d->x, d->stream_dtype, d->lnf_g, d->lnf_b, d->h, nullptr, nullptr, rows, D, 1e-5f,
                                stream)) != DW_OK) return rc;
     return gemm(d->h, D, d->lm_head, nullptr, d->ldv, D, d->logits, d->ldv, DW_BF16, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+static bool decode_desc_ok(const DwDecodeStep* d) {
+    return d && d->ids && d->tok_emb && d->pos_emb && d->layers && d->lm_head && d->x && d->h && d->qkv && d->o && d->a && d->logits;
+}
+
+extern "C" int dw_decode_step(const DwDecodeStep* d, void* stream) {
+    DW_CLEAR_ERR();
+    if (!decode_desc_ok(d)) return DW_EINVAL;
+    return decode_pass(d, nullptr, d->t, stream);
+}
+
+extern "C" int dw_decode_step_rows(const DwDecodeStep* d, const int32_t* row_t, int32_t max_t, void* stream) {
+    DW_CLEAR_ERR();
+    if (!decode_desc_ok(d) || !row_t || ((uintptr_t)row_t & 3)) return DW_EINVAL;
+    return decode_pass(d, row_t, max_t, stream);
 }

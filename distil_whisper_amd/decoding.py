@@ -448,14 +448,16 @@ ASSIST_TORCH_ENV = "DW_ASSIST_TORCH"
 
 
 def assist_pick_torch(logits, hist, first_pos, begin_index, eos_token_id=None, min_new_tokens=0, suppress=None,
-                      timestamp_rules=None):
+                      timestamp_rules=None, begin_suppress=None):
     """Greedy tokens int64 [B, n] from scores [B, n, V] whose row j predicts the token at sequence index first_pos + j (the torch
     path of oracle.ref_ops, of CPU runs, of unsupported sizes and of DW_ASSIST_TORCH=1; csrc/assist.hip `dw_assist_pick` is the
     kernel).  hist int64 [B, >= first_pos + n - 1]: the sequence those positions continue (history of the timestamp rules);
     begin_index: decoder prompt length; suppress: a mask of `processed_scores` (an f32 [V] vector with -inf at the suppressed ids reads
-    the same), or None.  No begin-suppress mask, as in the device path."""
+    the same), or None.  begin_suppress: the mask of the first generated position (None in `generate`, where an assistant switches
+    it off as in the reference; pseudo_label.PseudoLabeller keeps its own)."""
     return torch.stack([processed_scores(logits[:, j], hist, first_pos + j, begin_index=begin_index, eos=eos_token_id,
                                          no_eos=first_pos + j - begin_index < min_new_tokens, suppress=suppress,
+                                         first=first_pos + j == begin_index, begin_suppress=begin_suppress,
                                          timestamp_rules=timestamp_rules).argmax(-1)
                         for j in range(logits.shape[1])], 1)
 
@@ -478,9 +480,68 @@ def assist_accept_torch(own, draft, L, k, done, eos_token_id, fill):
     return new, done, n_ok
 
 
+def assist_pick_rows_torch(logits, tokens, lengths, j0, begin_index, eos_token_id=None, min_new_tokens=0, suppress=None,
+                           timestamp_rules=None, begin_suppress=None):
+    """`assist_pick_torch` with per-row positions (`dw_assist_pick_rows` is the kernel): scores [B, n, V] whose row (b, j) predicts
+    tokens[b, lengths[b] + j0 + j] from the history tokens[b, :lengths[b] + j0 + j]; lengths: B ints.  -> int64 [B, n]; a position
+    behind the buffer (a row that has ended at its end) is not judged and yields 0."""
+    B, n = logits.shape[:2]
+    own = torch.zeros((B, n), dtype=torch.long, device=logits.device)
+    for b, L in enumerate(lengths):
+        for j in range(n):
+            at = max(int(L), begin_index) + j0 + j
+            if at < tokens.shape[1]:
+                own[b, j] = assist_pick_torch(logits[b:b + 1, j:j + 1], tokens[b:b + 1], at, begin_index, eos_token_id, min_new_tokens,
+                                              suppress, timestamp_rules, begin_suppress)[0, 0]
+    return own
+
+
+def assist_accept_rows_torch(own, tokens, length, k, total, done, eos_token_id, fill):
+    """The bookkeeping of one round with per-row lengths as host arithmetic over torch tensors (`dw_assist_accept_rows` is the
+    kernel; include/dwamd.h states the rule): own int64 [B, >= k + 1] the target's choices at positions length[b] .. length[b] + k,
+    tokens int64 [B, total] with row b's k drafts at [length[b], length[b] + k), length int32 [B], done bool [B]; tokens, length
+    and done are updated in place.  Returns (pos_target, pos_assistant: lists of B ints, the start positions of the next round's
+    passes -- length - 1 and length - 2, 0 for a row that has ended --, result = [drafts accepted, drafts offered, every row done,
+    largest live length])."""
+    B = tokens.shape[0]
+    lens, fins, rows_own, rows_tok = length.tolist(), done.tolist(), own.tolist(), tokens.tolist()
+    acc = off = top = 0
+    pos_t, pos_a = [0] * B, [0] * B
+    for b in range(B):
+        L = min(max(lens[b], 1), total)
+        fin = bool(fins[b]) or L >= total
+        end = min(L + k, total - 1)
+        if not fin:
+            kb = end - L
+            m = 0
+            while m < kb and rows_own[b][m] == rows_tok[b][L + m]:
+                m += 1
+            w = 0
+            while w <= m:
+                c = rows_own[b][w]
+                tokens[b, L + w] = c
+                w += 1
+                if eos_token_id is not None and c == eos_token_id:
+                    fin = True
+                    break
+            acc += min(w, m)
+            off += kb
+            L += w
+            fin = fin or L >= total
+            length[b] = L
+        if fin:
+            if L <= end:
+                tokens[b, L:end + 1] = fill
+        else:
+            top = max(top, L)
+            pos_t[b], pos_a[b] = L - 1, L - 2
+        done[b] = fin
+    return pos_t, pos_a, [acc, off, int(bool(done.all())), top]
+
+
 def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_ids, max_new_tokens,
                            num_assistant_tokens=5, eos_token_id=None, suppress_tokens=None, min_new_tokens=0,
-                           pad_token_id=None, use_cache=True, timestamp_rules=None):
+                           pad_token_id=None, use_cache=True, timestamp_rules=None, per_row=False, begin_suppress_tokens=None):
     """Speculative (assisted) greedy decoding: the small `assistant` engine drafts `num_assistant_tokens` tokens, the
     `target` engine scores all of them in ONE decoder pass and keeps the longest draft prefix that equals its own
     greedy choices plus its next token -- the output is token-for-token what target-only greedy decoding produces.
@@ -507,7 +568,16 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
     host reads `result` = (accepted drafts, every row done) once per round -- the only synchronisation.  On other ops
     (oracle.ref_ops, CPU), with DW_ASSIST_TORCH=1, with use_cache=False or beyond `assist_supported` the round is
     `assist_pick_torch` / `assist_accept_torch`: the same algorithm, the same minimum over the rows.  Equal scores: the lower column
-    wins in the kernels (torch.argmax's order among equals is unspecified on the device).  Returns (ids [B, P + n], drafted, accepted)."""
+    wins in the kernels (torch.argmax's order among equals is unspecified on the device).  Returns (ids [B, P + n], drafted, accepted).
+
+    per_row=True (needs use_cache): every row accepts its OWN agreeing prefix and ends at its own EOS -- one row's rejected draft
+    costs the other rows nothing, which is what makes an assistant pay at batch sizes above a few (the minimum over 16 rows'
+    prefixes is close to zero for any model pair).  The rows then stand at different lengths, so from the second round on the
+    decoder passes run at per-row positions (`engine.decode_multi_rows`, dw_decode_step_rows) and the round is
+    `assist_pick_rows` / `assist_accept_rows` (`_assisted_rounds_device_rows`); on ops without them the same rounds run on
+    `assist_pick_torch` per row and `assist_accept_rows_torch`.  Every row's output is still that row's own greedy output;
+    drafted / accepted are summed over the rows that were live in a round.  begin_suppress_tokens (per_row only): excluded at
+    the first generated position, for the drafts and the verification alike."""
     dt, da = target.dims, assistant.dims
     B, P0 = prompt_ids.shape
     ids = prompt_ids.clone()
@@ -517,6 +587,16 @@ def assisted_greedy_decode(target, assistant, enc_target, enc_assistant, prompt_
         raise ValueError(f"prompt + max_new_tokens = {total} exceeds max_target_positions")
     fill = eos_token_id if pad_token_id is None else pad_token_id
     ops_t, ops_a = target.ops, assistant.ops
+    if begin_suppress_tokens and not per_row:
+        raise NotImplementedError("begin_suppress_tokens with an assistant are implemented for per_row=True")
+    if per_row:
+        if not use_cache:
+            raise NotImplementedError("per-row acceptance runs on the KV caches (use_cache=True)")
+        kernels = (all(hasattr(o, "assist_pick_rows") and hasattr(o, "assist_accept_rows") for o in (ops_t, ops_a))
+                   and ops_t.assist_supported(B, int(num_assistant_tokens)) and os.environ.get(ASSIST_TORCH_ENV, "0") in ("", "0"))
+        return _assisted_rounds_device_rows(target, assistant, enc_target, enc_assistant, prompt_ids, total, int(num_assistant_tokens),
+                                            eos_token_id, suppress_tokens, int(min_new_tokens), fill, timestamp_rules, kernels,
+                                            begin_suppress_tokens)
     if (use_cache and all(hasattr(o, "assist_pick") and hasattr(o, "assist_accept") for o in (ops_t, ops_a))
             and ops_t.assist_supported(B, int(num_assistant_tokens)) and os.environ.get(ASSIST_TORCH_ENV, "0") in ("", "0")):
         return _assisted_rounds_device(target, assistant, enc_target, enc_assistant, prompt_ids, total, int(num_assistant_tokens),
@@ -620,6 +700,121 @@ def _assisted_rounds_device(target, assistant, enc_target, enc_assistant, prompt
         ca["t"] = min(ca["t"], L + n_ok)
         L += n_ok + 1
     return tokens[:, :L].clone(), drafted, accepted
+
+
+def _assisted_rounds_device_rows(target, assistant, enc_target, enc_assistant, prompt_ids, total, num_assistant_tokens, eos_token_id,
+                                 suppress_tokens, min_new_tokens, fill, timestamp_rules, kernels=True, begin_suppress_tokens=None):
+    """The cached rounds of `assisted_greedy_decode(per_row=True)`: the state of `_assisted_rounds_device` plus, per row, `length`
+    (int32: the row's tokens so far), `done`, and the positions `pos_t` / `pos_a` from which the two models' next passes re-feed
+    the row.  The host reads `result` = (drafts accepted, drafts offered, every row done, largest live length) once per round and
+    nothing else; from it k = min(K, total - 1 - largest live length), so no live row drafts past the buffer.
+
+    Invariants, after every round, for every live row: the target's cache holds the K/V of the row's final tokens below
+    length - 1, the assistant's below length - 2.  (The target has seen every accepted draft but not its own last token; the
+    assistant has not seen the last draft it wrote, which is the only accepted draft it can miss.)  So the target's verify pass
+    starts at length - 1 with k + 1 tokens and the assistant catches up with a 2-token pass at length - 2, whose second row
+    drafts the first token.  The catch-up runs in EVERY round, also at k = 0: rounds without drafts follow one another while
+    rows reach total - 1 one after the other, and a row that skipped a catch-up would lag by more than two tokens.  Re-feeding a
+    position whose K/V are already valid rewrites them with values that may differ by a bf16 ulp from the first computation;
+    only drafts and positions the target verifies again read them.  Round 1 is the uniform round: every row stands at the prompt
+    length, so the prompt passes are `decode_multi`.  Rows that have ended are parked at position 0 (their passes stay inside
+    their cache, their results are never read).  kernels=False: the same rounds with `assist_pick_torch` per row and
+    `assist_accept_rows_torch` (which reads lengths on the host), and the invariants are checked as the passes are issued."""
+    dt, da = target.dims, assistant.dims
+    ops_t, ops_a = target.ops, assistant.ops
+    B, P0 = prompt_ids.shape
+    dev = prompt_ids.device
+    K = num_assistant_tokens
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    tokens = torch.full((B, total), 0 if fill is None else int(fill), dtype=torch.long, device=dev)
+    tokens[:, :P0].copy_(prompt_ids)
+    cur = torch.zeros((B, 1), dtype=torch.long, device=dev)
+    own = torch.zeros((B, K + 1), dtype=torch.long, device=dev)
+    done = torch.zeros((B,), dtype=torch.bool, device=dev)
+    length = torch.full((B,), P0, dtype=torch.int32, device=dev)
+    pos_t, pos_a, pos_d = (torch.zeros((B,), dtype=torch.int32, device=dev) for _ in range(3))
+    result = torch.zeros((4,), dtype=torch.int32, device=dev)
+    ar = torch.arange(K + 1, device=dev)
+
+    rk = rule_kwargs(timestamp_rules, eos_token_id)
+    rules = dict(min_new=min_new_tokens if eos >= 0 else 0, ts_begin=rk["ts_begin"], max_initial=rk["max_initial"], begin_index=P0,
+                 eos=eos)
+    sup, bsup = ({V: token_mask(ids, V, dev, torch.uint8 if kernels else torch.bool) for V in {dt.vocab, da.vocab}}
+                 for ids in (suppress_tokens, begin_suppress_tokens))
+    valid_t, valid_a = [0] * B, [0] * B                      # kernels=False: leading cache positions that hold final tokens' K/V
+
+    def fed(valid, start, n):                                # a pass may start at a valid position, not behind one
+        for b, p in enumerate(start):
+            assert p <= valid[b], "a cached pass would start behind the row's valid prefix"
+            valid[b] = p + n
+
+    def pick(ops, d, logits, n, j0, batch_rows, store):
+        if kernels:
+            ops.assist_pick_rows(logits, d.vocab, tokens, length, own, n=n, j0=j0, batch_rows=batch_rows, suppress=sup[d.vocab],
+                                 begin_suppress=bsup[d.vocab], store=store, cur=cur if store else None, **rules)
+            return
+        lens = length.tolist()
+        lg = torch.stack([logits[b * batch_rows:b * batch_rows + n, :d.vocab] for b in range(B)])
+        own[:, :n] = assist_pick_rows_torch(lg, tokens, lens, j0, P0, eos_token_id, rules["min_new"], sup[d.vocab], timestamp_rules,
+                                            bsup[d.vocab])
+        if store:
+            for b, L in enumerate(lens):
+                if L + j0 < total:
+                    tokens[b, L + j0] = own[b, 0]
+                    cur[b, 0] = own[b, 0]
+
+    ct = target.decode_init(enc_target, B, total)
+    ca = assistant.decode_init(enc_assistant, B, total)
+    drafted = accepted = 0
+    top, first, all_done = P0, True, False
+    while not all_done:
+        k = min(K, total - 1 - top)
+        if first:                                            # the uniform round: every row stands at P0
+            for j in range(k):
+                logits = assistant.decode_multi(tokens[:, :P0], ca)[P0 - 1:] if j == 0 else assistant.decode_step(cur, ca)
+                pick(ops_a, da, logits, 1, j, P0 if j == 0 else 1, True)
+            logits = target.decode_multi(tokens[:, :P0 + k], ct)[P0 - 1:]
+            rows = P0 + k
+            if not kernels:
+                fed(valid_t, [0] * B, P0 + k)
+                fed(valid_a, [0] * B, P0 + k - 1 if k else 0)
+        else:
+            if not kernels:
+                fed(valid_a, pos_a.tolist(), 2)
+            ids = tokens.gather(1, pos_a[:, None] + ar[None, :2])
+            logits = assistant.decode_multi_rows(ids, ca, pos_a, top - 2)[1:]       # catch-up; its second row drafts token 0
+            for j in range(k):
+                if j:
+                    torch.add(pos_a, 1 + j, out=pos_d)
+                    if not kernels:
+                        fed(valid_a, pos_d.tolist(), 1)
+                    logits = assistant.decode_multi_rows(cur, ca, pos_d, top - 1 + j)
+                pick(ops_a, da, logits, 1, j, 1 if j else 2, True)
+            if not kernels:
+                fed(valid_t, pos_t.tolist(), k + 1)
+            ids = tokens.gather(1, pos_t[:, None] + ar[None, :k + 1])
+            logits = target.decode_multi_rows(ids, ct, pos_t, top - 1)
+            rows = k + 1
+        pick(ops_t, dt, logits, k + 1, 0, rows, False)
+        if kernels:
+            ops_t.assist_accept_rows(own, tokens, length, k, total, result, done, pos_t, pos_a, eos=eos,
+                                     fill=-1 if fill is None else int(fill))
+            acc, off, fin, top = result.tolist()             # the round's one synchronisation
+        else:
+            pt, pa, (acc, off, fin, top) = assist_accept_rows_torch(own, tokens, length, k, total, done, eos_token_id,
+                                                                    0 if fill is None else int(fill))
+            pos_t.copy_(torch.tensor(pt, dtype=torch.int32))
+            pos_a.copy_(torch.tensor(pa, dtype=torch.int32))
+            for b, (L, f) in enumerate(zip(length.tolist(), done.tolist())):
+                if f:                                        # parked: whatever the passes leave in the row is never read
+                    valid_t[b] = valid_a[b] = total
+                    continue
+                assert valid_t[b] >= L - 1 and valid_a[b] >= L - 2, "the round left a live row's cache short of its invariant"
+                valid_t[b], valid_a[b] = L - 1, min(valid_a[b], L - 1)
+        all_done, first = bool(fin), False
+        drafted += off
+        accepted += acc
+    return tokens[:, :int(length.max().item())].clone(), drafted, accepted
 
 
 # DW_BEAM_TORCH=1 (read when a beam search starts): the step stays on the torch ops of `beam_step_torch` on every engine, as on ops

@@ -907,7 +907,7 @@ class WhisperEngine:
         cache["t"] += n
         return ws["logits"]     # (workspace of the cache: valid until the next pass with the same n)
 
-    def _decoder_layers_cached(self, x, cache, n):
+    def _decoder_layers_cached(self, x, cache, n, row_t=None):
         """The decoder layers of one cached pass over `n` new positions per row (x: [B*n, D] embedded inputs).  With
         few rows (B*n <= 32 / 64) the LayerNorm in front of each projection is computed inside the weight-streaming
         GEMM and the new K/V go straight into the cache (ops.gemm ln= / kv_append=); otherwise they are separate
@@ -915,12 +915,14 @@ class WhisperEngine:
         tests runs it).  `dw_decode_step` computes the same pass in fewer launches: since round 5 it runs LayerNorm + q
         projection + cross-attention in ONE kernel (`attn_decode_proj_kernel`, dw_debug_set key 7, default 4), whose fp32
         summation order differs from the GEMV's -- q may differ by one bf16 ulp between the two paths.  Tests that
-        compare them either pin `dw_debug_set(7, 12)` (the unfused sequence: exactly this one) or state a tolerance."""
+        compare them either pin `dw_debug_set(7, 12)` (the unfused sequence: exactly this one) or state a tolerance.
+        row_t (a list of B ints; `decode_multi_rows`): row b starts at position row_t[b] instead of cache["t"] -- its K/V go to
+        the cache rows row_t[b] + j by indexing and its self-attention is one `ops.attn_fwd` call over its own row_t[b] + n keys."""
         ops, st, d = self.ops, self.st, self.dims
         B, t, ML = cache["B"], cache["t"], cache["max_len"]
         D, H, Lk = d.d_model, d.heads, d.max_src
         rows = B * n
-        fuse_ln, fuse_kv = rows <= 32 and D <= 1280, rows <= 64
+        fuse_ln, fuse_kv = rows <= 32 and D <= 1280, rows <= 64 and row_t is None
         causal = 2 if n > 1 else False
         for i in range(d.dec_layers):
             p = f"model.decoder.layers.{i}"
@@ -930,9 +932,17 @@ class WhisperEngine:
             h = x if fuse_ln else ops.layernorm_fwd(x, *ln1, save_stats=False)[0]
             qkv = ops.gemm(h, av["wqkv"], bias=av["bqkv"], ln=ln1[:2] if fuse_ln else None,
                            kv_append=(kvc, D, n, ML, t) if fuse_kv else None)
-            if not fuse_kv:
+            if row_t is not None:
+                o = ops.empty((rows, D), self.lowp)
+                for b, tb in enumerate(row_t):
+                    kvb = kvc.view(B, ML, 2 * D)[b]
+                    kvb[tb:tb + n].copy_(qkv[b * n:(b + 1) * n, D:])
+                    ops.attn_fwd(qkv[b * n:(b + 1) * n, :D], kvb[:tb + n, :D], kvb[:tb + n, D:], 1, H, n, tb + n, causal, 0.125,
+                                 out=o[b * n:(b + 1) * n])
+            elif not fuse_kv:
                 kvc.view(B, ML, 2 * D)[:, t:t + n].copy_(qkv[:, D:].view(B, n, 2 * D))   # append this pass's K/V
-            o, _ = ops.attn_fwd(qkv[:, :D], kvc[:, :D], kvc[:, D:], B, H, n, t + n, causal, 0.125, kv_batch_rows=ML)
+            if row_t is None:
+                o, _ = ops.attn_fwd(qkv[:, :D], kvc[:, :D], kvc[:, D:], B, H, n, t + n, causal, 0.125, kv_batch_rows=ML)
             x = ops.gemm(o, av["wo"], bias=av["bo"], residual=x, round_res=True, out_dtype=self.stream)
             cv = st.attn_views(f"{p}.encoder_attn")
             ln2 = (st.p[f"{p}.encoder_attn_layer_norm.weight"], st.p[f"{p}.encoder_attn_layer_norm.bias"], 1e-5)
@@ -998,6 +1008,39 @@ class WhisperEngine:
         logits = ops.gemm(hf, e_pad)
         cache["t"] = t + n
         return logits
+
+    def decode_multi_rows(self, ids, cache, row_t, max_t):
+        """`decode_multi` with row b at its own position: ids int64 [B, n] are the tokens at positions row_t[b] .. row_t[b] + n - 1
+        of row b (row_t int32 [B] on the ids' device; max_t: a host bound, row_t <= max_t and max_t + n <= max_len) -> logits
+        low-precision [B*n, ldv], row b*n + j = position row_t[b] + j of row b.  Position embeddings, the cache rows written and the
+        keys a query sees (<= row_t[b] + j) all follow the row; cache rows below row_t[b] must be valid.  cache["t"] is neither read
+        nor moved: the caller owns the positions (speculative decoding with per-row acceptance, decoding.assisted_greedy_decode).
+        On the HIP path this is ONE call of dw_decode_step_rows, which never brings row_t to the host; on other ops (oracle.ref_ops,
+        CPU) the per-kernel form: position rows gathered by indexing, K/V written by indexing, one `ops.attn_fwd` per row."""
+        ops, st, d = self.ops, self.st, self.dims
+        B, ML = cache["B"], cache["max_len"]
+        n = ids.shape[1]
+        assert ids.shape[0] == B and row_t.dtype == torch.int32 and row_t.numel() == B
+        assert 0 <= max_t and max_t + n <= ML and max_t + n <= d.max_tgt
+        if self.use_c_decode and hasattr(ops, "decode_pass_rows"):
+            desc, ws, _, _ = self._decode_desc(cache, n)
+            ids = ids.contiguous()
+            desc.ids = ids.data_ptr()
+            ops.decode_pass_rows(desc, row_t, max_t)
+            return ws["logits"]     # (workspace of the cache: valid until the next pass with the same n)
+        rows = [int(t) for t in row_t.tolist()]
+        assert all(0 <= t <= max_t for t in rows)
+        f32 = self.stream == torch.float32
+        tok = (st.p if f32 else st.s)["model.decoder.embed_tokens.weight"]
+        at = (torch.tensor(rows, device=ids.device)[:, None] + torch.arange(n, device=ids.device)[None, :]).reshape(-1)
+        pos = (st.p if f32 else st.s)["model.decoder.embed_positions.weight"][at]
+        x = ops.embed_fwd(ids.reshape(1, B * n).contiguous(), tok, pos.contiguous(), torch.float32 if f32 else self.lowp)
+        x = self._decoder_layers_cached(x, cache, n, row_t=rows)
+        hf, _, _ = ops.layernorm_fwd(x, st.p["model.decoder.layer_norm.weight"], st.p["model.decoder.layer_norm.bias"],
+                                     1e-5, save_stats=False)
+        eo = st.entries["model.decoder.embed_tokens.weight"][0]
+        e_pad = st.S[eo:eo + self.ldv * d.d_model].view(self.ldv, d.d_model)
+        return ops.gemm(hf, e_pad)
 
     # ---- backward --------------------------------------------------------------------------------------------------
     def _bias_grad(self, name):

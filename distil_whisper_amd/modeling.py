@@ -812,6 +812,9 @@ class WhisperForConditionalGeneration(nn.Module):
         list of the reference (run_distillation.py:1524-1528, run_eval.py:690-739, 806-844): greedy search over one
         30 s window per row with language / task / timestamp / prompt_ids prefixes, the suppress / begin-suppress /
         min-new-tokens / timestamp logits rules, `assistant_model` (speculative decoding), `encoder_outputs`.
+        `assistant_per_row=True` (with an assistant, single window, KV caches): every row of the batch accepts its own agreeing
+        draft prefix instead of the batch minimum and ends at its own EOS (decoding.assisted_greedy_decode `per_row`); without an
+        assistant a ValueError, inside the seek loop or with `use_cache=False` a NotImplementedError before anything is decoded.
         The token loop is decoding.GreedyDecoder (KV cache; `use_graphs` replays the per-position launch sequence from
         HIP graphs; `use_cache=False` re-decodes the whole prefix every step and exists as a cross-check).
         `num_beams > 1` runs decoding.beam_search_decode (TF `_beam_search`; its step is two kernel entries, dw_beam_candidates and
@@ -868,7 +871,7 @@ class WhisperForConditionalGeneration(nn.Module):
         # plain sampling: as in the reference's generate_with_fallback (TF:generation_whisper.py `do_sample = temperature is not
         # None and temperature > 0.0`), a positive `temperature` IS the switch -- `do_sample=True` alone decodes greedily
         sample_temp = float(temps[0]) if (not uses_fallback and temps[0] is not None and temps[0] > 0.0) else None
-        engine_keys = ("encoder_outputs", "assistant_model", "decoder_input_ids", "use_cache")
+        engine_keys = ("encoder_outputs", "assistant_model", "decoder_input_ids", "use_cache", "assistant_per_row")
         unknown = [k for k in kwargs if k not in G._CONFIG_KEYS and k not in engine_keys]
         if unknown:
             raise ValueError(f"The following `model_kwargs` are not used by the model: {unknown} (note: typos in the "
@@ -884,6 +887,16 @@ class WhisperForConditionalGeneration(nn.Module):
             raise NotImplementedError("num_return_sequences > 1 is not implemented on the MI355X path")
         if num_beams == 1 and getattr(gc, "length_penalty", None) not in (None, 1.0):
             raise NotImplementedError("length_penalty without beam search is not implemented on the MI355X path")
+        # ---- assistant_per_row=True: speculative decoding in which every row accepts its own draft prefix (decoding.
+        # assisted_greedy_decode per_row).  Single-window greedy decoding on the KV caches only; refused before anything is decoded
+        per_row = bool(kwargs.get("assistant_per_row", False))
+        if per_row:
+            if kwargs.get("assistant_model") is None:
+                raise ValueError("assistant_per_row=True needs an assistant_model")
+            if kwargs.get("use_cache", True) is False:
+                raise NotImplementedError("assistant_per_row=True runs on the KV caches (not with use_cache=False)")
+            if num_beams > 1:
+                raise NotImplementedError("assistant_per_row=True cannot be combined with beam search")
         # history-dependent processors / sampling (GenerationMixin's repetition penalty, no-repeat n-gram, temperature / top-k /
         # top-p sampling): on the single-call KV-cache decoder (decoding.GreedyDecoder `soft`); elsewhere they raise below
         soft = None
@@ -993,6 +1006,10 @@ class WhisperForConditionalGeneration(nn.Module):
                     raise NotImplementedError("sampling (a positive temperature as a plain switch) is implemented for "
                                               "single-window decoding, not inside the timestamp seek loop, on the MI355X path "
                                               "(a temperature tuple runs the seek loop's sampled fallback passes)")
+                if per_row:
+                    raise NotImplementedError("assistant_per_row=True is implemented for single-window decoding, not inside the "
+                                              "timestamp seek loop (return_timestamps=True without force_unique_generate_call, or "
+                                              "more than 30 s of input), on the MI355X path")
                 if want_scores or want_logits:
                     raise NotImplementedError("output_scores / output_logits inside the timestamp seek loop (return_timestamps=True "
                                               "without force_unique_generate_call, or more than 30 s of input) are not implemented "
@@ -1094,7 +1111,7 @@ class WhisperForConditionalGeneration(nn.Module):
                 getattr(getattr(assistant_model, "generation_config", None), "num_assistant_tokens", None) or 5
             seqs, self.last_drafted, self.last_accepted = assisted_greedy_decode(
                 eng, assistant_model.engine, enc, enc_a, ids, max_new, int(k), eos, suppress_tokens=suppress,
-                min_new_tokens=min_new, pad_token_id=pad, timestamp_rules=a_ts_rules)
+                min_new_tokens=min_new, pad_token_id=pad, timestamp_rules=a_ts_rules, per_row=per_row)
         elif use_cache:
             from .decoding import GreedyDecoder
             ts_rules = None

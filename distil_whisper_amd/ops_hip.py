@@ -53,6 +53,7 @@ class DwDecodeStep(C.Structure):
 _SIGS = {
     "dw_version": ([], C.c_int),
     "dw_decode_step": ([C.POINTER(DwDecodeStep), C.c_void_p], C.c_int),
+    "dw_decode_step_rows": ([C.POINTER(DwDecodeStep), C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
     "dw_logmel": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                    C.c_void_p], C.c_int),
     "dw_gemm_bf16": ([C.POINTER(DwGemm), C.c_void_p], C.c_int),
@@ -119,6 +120,11 @@ _SIGS = {
                         C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
     "dw_assist_accept": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                           C.c_void_p, C.c_void_p], C.c_int),
+    "dw_assist_pick_rows": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                             C.c_void_p], C.c_int),
+    "dw_assist_accept_rows": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "dw_cross_attn_probs": ([C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int64,
                                                                                                     C.c_float, C.c_void_p], C.c_int),
     "dw_align_prepare": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -389,6 +395,14 @@ class HipOps:
         e0 = self._t0()
         self._chk(self.lib.dw_decode_step(C.byref(desc), self._stream()), "decode_step")
         self._t1(e0, "decode_step", 0.0)
+
+    def decode_pass_rows(self, desc, row_t, max_t):
+        """The pass of `decode_pass` with row b starting at position row_t[b] (dw_decode_step_rows): row_t int32 [batch] on the
+        device, max_t the host's upper bound of its entries (launch and LDS sizing; max_t + n_new <= max_len)."""
+        assert row_t.dtype == torch.int32 and row_t.is_contiguous() and row_t.numel() >= desc.batch and row_t.device == self.device
+        e0 = self._t0()
+        self._chk(self.lib.dw_decode_step_rows(C.byref(desc), _p(row_t), int(max_t), self._stream()), "decode_step_rows")
+        self._t1(e0, "decode_step_rows", 0.0)
 
     def layernorm_fwd(self, x, gamma, beta, eps=1e-5, save_stats=True, out=None):
         """x, out: 2-D with unit column stride; their row pitches may exceed the row length (padded activation buffers)."""
@@ -802,6 +816,41 @@ class HipOps:
         assert (done is None and eos < 0) or (done.dtype == torch.bool and done.is_contiguous() and done.numel() >= B)
         self._chk(self.lib.dw_assist_accept(_p(own), own.stride(0), _p(tokens), tokens.stride(0), B, int(L), int(k), int(eos),
                                             int(fill), _p(done), _p(result), self._stream()), "assist_accept")
+
+    def assist_pick_rows(self, logits, V, tokens, length, own, *, n=1, j0=0, batch_rows=None, suppress=None, begin_suppress=None,
+                         min_new=0, ts_begin=-1, max_initial=-1, begin_index=1, eos=-1, store=False, cur=None):
+        """`assist_pick` with the first judged position of row b read from the device: length int32 [B], row b * batch_rows + j of
+        the logits predicts tokens[b, length[b] + j0 + j] (include/dwamd.h dw_assist_pick_rows).  store (n == 1): the assistant's
+        draft step number j0 of the round."""
+        B, n = tokens.shape[0], int(n)
+        rows = n if batch_rows is None else int(batch_rows)
+        self._check_select(logits, (B - 1) * rows + n, V, suppress, begin_suppress)
+        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.shape[1] > begin_index >= 1
+        assert length.dtype == torch.int32 and length.is_contiguous() and length.numel() >= B
+        assert own.dtype == torch.int64 and own.stride(1) == 1 and own.shape[0] >= B and own.shape[1] >= n
+        assert rows >= n >= 1 and logits.shape[1] >= V and j0 >= 0
+        if store:
+            assert n == 1 and cur is not None and cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() >= B
+        self._chk(self.lib.dw_assist_pick_rows(
+            _p(logits), B, n, int(V), logits.stride(0), rows, _p(suppress), _p(begin_suppress), int(min_new), int(ts_begin),
+            int(max_initial), _p(tokens), tokens.shape[1], _p(length), int(j0), int(begin_index), int(eos), _p(own), own.stride(0),
+            int(store), _p(cur) if store else None, self._stream()), "assist_pick_rows")
+
+    def assist_accept_rows(self, own, tokens, length, k, total, result, done, pos_target, pos_assistant, *, eos=-1, fill=-1):
+        """The bookkeeping of one round with per-row lengths (include/dwamd.h dw_assist_accept_rows): own int64 [B, >= k + 1] from
+        `assist_pick_rows(n=k + 1)`, row b's k drafts at tokens[b, length[b]:length[b] + k]; length int32 [B], done bool [B],
+        pos_target / pos_assistant int32 [B] and result int32 [4] = (drafts accepted, drafts offered, every row done, largest live
+        length) are written."""
+        B = tokens.shape[0]
+        assert own.dtype == torch.int64 and own.stride(1) == 1 and own.shape[0] >= B and own.shape[1] >= k + 1 and k >= 0
+        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.shape[1] >= total >= 2
+        for t in (length, pos_target, pos_assistant):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= B
+        assert result.dtype == torch.int32 and result.is_contiguous() and result.numel() >= 4
+        assert done.dtype == torch.bool and done.is_contiguous() and done.numel() >= B
+        self._chk(self.lib.dw_assist_accept_rows(_p(own), own.stride(0), _p(tokens), tokens.stride(0), B, int(k), int(total), int(eos),
+                                                 int(fill), _p(length), _p(done), _p(pos_target), _p(pos_assistant), _p(result),
+                                                 self._stream()), "assist_accept_rows")
 
     # ---- token-level timestamps (csrc/align.hip; TF:generation_whisper.py:241-381) ------------------------------------
     def cross_attn_probs(self, q, k, heads, probs, slot0, B, L, Lk, kv_batch_rows=None, scale=0.125):

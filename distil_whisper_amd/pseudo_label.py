@@ -46,7 +46,7 @@ class PseudoLabeller:
     def __init__(self, model, feature_extractor, batch_size=16, max_new_tokens=255, prompt_ids=None, eos_token_id=None,
                  timestamp_rules=None, use_graphs=None, rank=0, world=1, suppress_tokens=None,
                  begin_suppress_tokens=None, num_beams=1, overlap=False, decode_cus=64, repetition_penalty=None,
-                 no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None):
+                 no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None, assistant_model=None, num_assistant_tokens=5):
         from .longform import history_soft
         self.model, self.fe = model, feature_extractor
         self.B, self.max_new = int(batch_size), int(max_new_tokens)
@@ -64,6 +64,22 @@ class PseudoLabeller:
                                                         no_repeat_ngram_size=soft["no_repeat_ngram_size"])
         if soft is not None and soft.get("sequence_bias") is not None:
             self._history_kw["sequence_bias"] = soft["sequence_bias"]
+        # assistant_model: speculative decoding of the plain greedy path with per-row acceptance (decoding.assisted_greedy_decode
+        # per_row=True; run_eval.py:578-599 gives the teacher its distilled student) -- every pack keeps its own accepted drafts,
+        # the labels are the teacher's own greedy labels.  A decoder-only WhisperForCausalLM drafts on the teacher's encoder output.
+        self.assistant, self.num_assistant_tokens = assistant_model, int(num_assistant_tokens)
+        if assistant_model is not None:
+            for on, what in ((self.num_beams > 1, "num_beams > 1"), (timestamp_rules is not None, "timestamp_rules (the seek loop)"),
+                             (soft is not None, "repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids")):
+                if on:
+                    raise NotImplementedError(f"PseudoLabeller(assistant_model=) with {what} is not implemented on the MI355X path "
+                                              "(the assistant drafts for plain greedy decoding)")
+            if self.num_assistant_tokens < 1:
+                raise ValueError("num_assistant_tokens must be at least 1")
+            from .modeling import _assistant_shares_encoder
+            self._assistant_own_encoder = not (_assistant_shares_encoder(assistant_model, model.dims))
+            self._assist_kw = dict(eos_token_id=eos_token_id, suppress_tokens=suppress_tokens,
+                                   begin_suppress_tokens=begin_suppress_tokens, per_row=True)
         d = model.dims
         dev = model.ops.device
         self.dev = dev
@@ -106,12 +122,25 @@ class PseudoLabeller:
 
         batches = [mine[b0:b0 + self.B] for b0 in range(0, len(mine), self.B)]
         plain = not (self._ts_rules is not None and self.num_beams == 1) and self.num_beams == 1
+        encode = lambda b: model.engine.encode(wave_to_features(b), save=False)[0]
+        decode = lambda enc: self.decoder.run(enc, prompt, self.max_new)
+        if self.assistant is not None:
+            from .decoding import assisted_greedy_decode
+            am = self.assistant
+            am._sync_shadow()
+            if self._assistant_own_encoder:                # (its encoder differs from the teacher's: both encode the batch)
+                def encode(b):
+                    feats = wave_to_features(b)
+                    return model.engine.encode(feats, save=False)[0], am.engine.encode(feats, save=False)[0]
+            else:
+                def encode(b, _enc=encode):
+                    e = _enc(b)
+                    return e, e.to(am.engine.lowp)
+            decode = lambda encs: assisted_greedy_decode(model.engine, am.engine, encs[0], encs[1], prompt, self.max_new,
+                                                         self.num_assistant_tokens, **self._assist_kw)[0]
         if plain:
             from .longform import two_stage_pipeline
-            for batch, ids in two_stage_pipeline(self, model.ops, self.dev, batches,
-                                                 lambda b: model.engine.encode(wave_to_features(b), save=False)[0],
-                                                 lambda enc: self.decoder.run(enc, prompt, self.max_new), self.overlap,
-                                                 self.decode_cus):
+            for batch, ids in two_stage_pipeline(self, model.ops, self.dev, batches, encode, decode, self.overlap, self.decode_cus):
                 for r, pi in enumerate(batch):
                     row = ids[r, self.prompt.numel():].tolist()
                     if self.eos is not None and self.eos in row:

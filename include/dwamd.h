@@ -399,6 +399,34 @@ int dw_assist_pick(const void* logits, int B, int n, int V, int64_t ld, int64_t 
  * they hold.  One workgroup, one thread per row: B <= 1024 and k <= 1024, else DW_EUNSUP (the caller keeps its torch step). */
 int dw_assist_accept(const int64_t* own, int64_t own_ld, int64_t* tokens, int64_t tok_ld, int B, int L, int k, int eos, int fill,
                      uint8_t* done, int32_t* result, void* stream);
+/* Per-row acceptance: every row keeps its own length len[b] (int32 [B], device memory that the host never reads), so a rejected
+ * draft of one row costs the other rows nothing; the decoder passes of such a round are dw_decode_step_rows.
+ * dw_assist_pick_rows: dw_assist_pick with the host's L replaced by the device's len[b] + j0: the row at element offset
+ * (b * batch_rows + j) * ld predicts tokens[b][len[b] + j0 + j] from the history tokens[b][0, len[b] + j0 + j); begin_suppress
+ * where that index == begin_index, eos masked while it is < begin_index + min_new, every rule as in dw_assist_pick (the same
+ * calls into select_rules.h).  len[b] >= begin_index (smaller values are read as begin_index).  store != 0 (n == 1; the
+ * assistant's draft step number j0 of the round): the token also goes to tokens[b][len[b] + j0] and cur[b].  A position
+ * >= tok_ld (a row that has ended at the end of the buffer) is not judged: own[b][j] = 0, nothing else is written.  tok_ld >
+ * begin_index.  One workgroup per (j, b); B <= 65535. */
+int dw_assist_pick_rows(const void* logits, int B, int n, int V, int64_t ld, int64_t batch_rows, const uint8_t* suppress,
+                        const uint8_t* begin_suppress, int min_new, int ts_begin, int max_initial, int64_t* tokens, int64_t tok_ld,
+                        const int32_t* len, int j0, int begin_index, int eos, int64_t* own, int64_t own_ld, int store,
+                        int64_t* cur, void* stream);
+/* dw_assist_accept_rows: with own [B][own_ld] from dw_assist_pick_rows(n = k + 1, j0 = 0) and row b's drafts at tokens[b][len[b],
+ * len[b] + k).  A row is live when done[b] == 0 and len[b] < total; for a live row with kb = min(k, total - 1 - len[b]) drafts
+ * offered (the caller sizes k so that kb == k): m_b = the number of leading j < kb with own[b][j] == tokens[b][len[b] + j]; for
+ * j = 0 .. m_b in order c = own[b][j], tokens[b][len[b] + j] = c, and the row ends there when c == eos (eos < 0: never); len[b]
+ * becomes the index behind the last token written, and the row also ends when that reaches `total`.  A row that has ended, in
+ * this call or before, has tokens[b][len[b] .. min(old len[b] + k, total - 1)] = fill (the drafts behind its end), done[b] = 1
+ * and is parked: pos_target[b] = pos_assistant[b] = 0.  A row still live: done[b] = 0, pos_target[b] = len[b] - 1 and
+ * pos_assistant[b] = len[b] - 2, the positions from which the next round's passes re-feed it (the target's cache is valid below
+ * len - 1, the assistant's below len - 2).  done uint8 [B] in/out (required, also for eos < 0).  result int32 [4] = {drafts
+ * accepted, summed over the rows live on entry: min(tokens written, m_b); drafts offered to them: the sum of kb; 1 when no row is
+ * live on return; the largest len among the rows live on return, 0 when there is none}.  tok_ld >= total >= 2.  One workgroup, one
+ * thread per row: B <= 1024 and k <= 1024, else DW_EUNSUP. */
+int dw_assist_accept_rows(const int64_t* own, int64_t own_ld, int64_t* tokens, int64_t tok_ld, int B, int k, int total, int eos,
+                          int fill, int32_t* len, uint8_t* done, int32_t* pos_target, int32_t* pos_assistant, int32_t* result,
+                          void* stream);
 
 /* ---- a11: one decoder pass of cached greedy decoding as ONE call (the `decode_step` entry of SURVEY.md 8b).
  * Replaces `WhisperDecoder.forward` + `proj_out` on the cache branch (TF:modeling_whisper.py:690-795, 312-335, 1080)
@@ -442,6 +470,19 @@ typedef struct DwDecodeStep {
     void* logits;                /* out: bf16 [rows][ldv] */
 } DwDecodeStep;
 int dw_decode_step(const DwDecodeStep* d, void* stream);
+/* dw_decode_step_rows: the same pass with row b of the batch starting at position row_t[b] instead of d->t (which is ignored):
+ * its n_new tokens take the position embeddings row_t[b] + j, their K / V are written to rows row_t[b] + j of the row's
+ * self-attention cache, query j sees the keys [0, row_t[b] + j]; cross-attention, LayerNorms, GEMMs and the LM head are the
+ * launches of dw_decode_step.  Cache rows of a sequence below row_t[b] must be valid; rows outside [row_t[b], row_t[b] + n_new)
+ * are not written.  row_t: int32 [batch] in DEVICE memory, read by the kernels and never by the host (speculative decoding with
+ * per-row acceptance writes it in dw_assist_accept_rows); max_t: a host bound, row_t[b] <= max_t and max_t + n_new <= max_len,
+ * used for launch and LDS sizing only -- the kernels read an entry outside [0, max_t] as the nearer end of that range, so no
+ * entry can address past the row's cache.  Three launches differ from dw_decode_step: the embedding, the K/V append (the QKV GEMM
+ * runs without its fused append) and the self-attention, a kernel for few queries against per-row key counts: n_new <= 32 and
+ * n_new * (64 + max_t + n_new) * 4 + 8320 <= 65536 bytes of LDS (n_new = 6 at any max_len <= 2000), batch <= 65535, else
+ * DW_EUNSUP.  DW_EINVAL: what dw_decode_step refuses, a null or misaligned row_t, max_t < 0, max_t + n_new > max_len.  Refused
+ * calls launch nothing.  Nothing is allocated, nothing synchronises. */
+int dw_decode_step_rows(const DwDecodeStep* d, const int32_t* row_t, int32_t max_t, void* stream);
 
 /* ---- token-level timestamps (TF:generation_whisper.py:241-381 `_extract_token_timestamps`, :43-61 `_median_filter`, :64-115
  * `_dynamic_time_warping`; reached from `generate(return_token_timestamps=True)`, TF:1146-1157).  The reference collects every
