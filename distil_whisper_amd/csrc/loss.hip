@@ -104,8 +104,12 @@ __global__ __launch_bounds__(LOSS_NT) void loss_row_kernel(const bf16* s_logits,
                 if (i + e < V) {
                     const float s = bf2f(a[e]), t = bf2f(b[e]);
                     const float p1 = __expf(s - ms) * i1;
-                    const float pS = __expf((s - ms) * invT) * iS;
-                    const float pT = __expf((t - mt) * invT) * iT;
+                    // both products rounded before the subtraction (a compiler-chosen contraction of one of them leaves its rounding
+                    // error behind): student == teacher gives a KL gradient of exactly zero
+                    float pS = __expf((s - ms) * invT) * iS;
+                    float pT = __expf((t - mt) * invT) * iT;
+                    asm("" : "+v"(pS));
+                    asm("" : "+v"(pT));
                     g = gce * (p1 - ((int64_t)(i + e) == label ? 1.f : 0.f)) + gkl * (pS - pT);
                 }
                 o[e] = f2bf(g);

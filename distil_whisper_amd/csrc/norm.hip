@@ -164,7 +164,11 @@ __global__ __launch_bounds__(256) void ln_fwd_persist_kernel(const float* x, con
 // bf16 input (the teacher's residual stream) with 16-byte accesses: 8 elements per lane per vector.  With 8-byte loads the
 // row of a bf16 stream is half as many bytes per request as an fp32 row and the kernel ran at 3.0 TB/s against 4.5 for
 // fp32 input (tools/stream_kernels_bench.py).
-template <int NV8>
+// A16 = false: the same lane layout and arithmetic through 8-byte accesses, for a pitch that is a multiple of 4 elements only or a
+// base that is 8- but not 16-byte aligned -- the values (and so y, mean, rstd) do not depend on where the buffers lie.  The 4-element
+// kernel above sums a row in another order; it took these cases before and gave other last bits
+// (tests/test_training_kernels_edges_gpu.py, bf16 fallback at 5 rows x 512).
+template <int NV8, bool A16>
 __global__ __launch_bounds__(256) void ln_fwd_bf16x8_kernel(const bf16* x, const float* gamma, const float* beta, bf16* y,
                                                             float* mean, float* rstd, int rows, int cols, float eps, long ldx, long ldy) {
     const int lane = threadIdx.x & 63;
@@ -177,7 +181,14 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16x8_kernel(const bf16* x, const
     for (int j = 0; j < NV8; ++j) {
         const int idx = lane + 64 * j;
         if (idx < nvec) {
-            const bf16x8 t = ln_load_in((const bf16x8*)(x + (long)row * ldx + idx * 8));
+            bf16x8 t;
+            if constexpr (A16) t = ln_load_in((const bf16x8*)(x + (long)row * ldx + idx * 8));
+            else {
+                const bf16x4 t0 = ln_load_in((const bf16x4*)(x + (long)row * ldx + idx * 8));
+                const bf16x4 t1 = ln_load_in((const bf16x4*)(x + (long)row * ldx + idx * 8 + 4));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { t[e] = t0[e]; t[e + 4] = t1[e]; }
+            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) { v[j][e] = bf2f(t[e]); s += v[j][e]; }
         }
@@ -207,18 +218,81 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16x8_kernel(const bf16* x, const
                 o[e] = f2bf((v[j][e] - mu) * rs * g0[e] + b0[e]);
                 o[e + 4] = f2bf((v[j][e + 4] - mu) * rs * g1[e] + b1[e]);
             }
-            ln_store<1>((bf16x8*)(y + (long)row * ldy + idx * 8), o);
+            if constexpr (A16) ln_store<1>((bf16x8*)(y + (long)row * ldy + idx * 8), o);
+            else {
+                bf16x4 o0, o1;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { o0[e] = o[e]; o1[e] = o[e + 4]; }
+                ln_store<1>((bf16x4*)(y + (long)row * ldy + idx * 8), o0);
+                ln_store<1>((bf16x4*)(y + (long)row * ldy + idx * 8 + 4), o1);
+            }
         }
     }
     if (lane == 0 && mean) { mean[row] = mu; rstd[row] = rs; }
 }
 
+// The per-element arithmetic of the two backward kernels with every rounding pinned: which products the compiler contracts into a
+// following add depends on the code around them, and the plain and the prefetching kernel gave residual gradients that differed in
+// the last bit (tests/test_training_kernels_edges_gpu.py, key 21 = 1 at 517 x 1028).  ln_round() makes a value opaque to that choice.
+__device__ __forceinline__ float ln_round(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+#define LN_BWD_TERMS(XV, DV)                                                                                          \
+    do {                                                                                                              \
+        const float xh_ = ln_round(((XV) - mu) * rs), g_ = ln_round((DV) * gm[j][e]);                                 \
+        xh[j][e] = xh_;                                                                                               \
+        g[j][e] = g_;                                                                                                 \
+        c1 += g_;                                                                                                     \
+        c2 = __builtin_fmaf(g_, xh_, c2);                                                                             \
+        ag[j][e] = __builtin_fmaf((DV), xh_, ag[j][e]);                                                               \
+        ab[j][e] += (DV);                                                                                             \
+    } while (0)
+__device__ __forceinline__ float ln_bwd_dx(float g, float xh, float c1, float c2, float rs) {
+    return ln_round(rs * __builtin_fmaf(-xh, c2, ln_round(g - c1)));
+}
+
+// The three column sums in two stages, like dw_sumsq_f32: each workgroup of the backward stores its share of every column as float64
+// into sums[3][gridDim.x][cols] (ln_bwd_put_sums) and ln_bwd_sums_kernel adds the shares in a fixed order, rounding once into
+// dgamma / dbeta / dres_colsum.  As fp32 atomics into those words (up to 1024 additions in arrival order per column) the sums had
+// 5 x (dgamma) to 16 x (column sums, 4101 x 768) the error of a pairwise fp32 sum and changed from run to run
+// (tests/test_training_kernels_edges_gpu.py, module docstring).
+__device__ __forceinline__ void ln_bwd_put_sums(double* sums, bool colsum, int cols, int col, double sg, double sb, double sc) {
+    const long per = (long)gridDim.x * cols;
+    double* dst = sums + (long)blockIdx.x * cols + col;
+    dst[0] = sg;
+    dst[per] = sb;
+    if (colsum) dst[2 * per] = sc;
+}
+// grid (ceil(cols / 64), 3), 1024 threads: 16 lanes per column, each over every 16th share, then the 16 in order
+__global__ __launch_bounds__(1024) void ln_bwd_sums_kernel(const double* sums, int shares, float* dgamma, float* dbeta,
+                                                           float* dres_colsum, int cols) {
+    __shared__ double part[16][64];
+    float* out = blockIdx.y == 0 ? dgamma : blockIdx.y == 1 ? dbeta : dres_colsum;
+    if (!out) return;
+    const int c = threadIdx.x & 63, seg = threadIdx.x >> 6;
+    const int col = blockIdx.x * 64 + c;
+    double s = 0.;
+    if (col < cols) {
+        const double* src = sums + (long)blockIdx.y * shares * cols + col;
+        for (int b = seg; b < shares; b += 16) s += src[(long)b * cols];
+    }
+    part[seg][c] = s;
+    __syncthreads();
+    if (seg == 0 && col < cols) {
+        double t = 0.;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += part[k][c];
+        out[col] = (float)((double)out[col] + t);
+    }
+}
+
 template <bool XBF, int NV, int NW>
 __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const bf16* dy, const void* x, const float* mean,
                                                      const float* rstd, const float* gamma, float* dres,
-                                                     int accumulate, float* dgamma, float* dbeta, bf16* dres_lowp,
+                                                     int accumulate, bf16* dres_lowp,
                                                      float* dres_colsum, int rows, int cols, long lddy, long ldx, long lddres,
-                                                         long ldlowp) {
+                                                         long ldlowp, double* sums) {
     __shared__ float red[3 * NW * 512];  // [dgamma|dbeta|colsum][wave][512-column window]
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -242,14 +316,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const bf16* dy, const v
                 const f32x4 xv = ld4b<XBF>(x, (long)row * ldx + idx * 4);
                 const f32x4 dv = ld4b<true>(dy, (long)row * lddy + idx * 4);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xh[j][e] = (xv[e] - mu) * rs;
-                    g[j][e] = dv[e] * gm[j][e];
-                    c1 += g[j][e];
-                    c2 += g[j][e] * xh[j][e];
-                    ag[j][e] += dv[e] * xh[j][e];
-                    ab[j][e] += dv[e];
-                }
+                for (int e = 0; e < 4; ++e) LN_BWD_TERMS(xv[e], dv[e]);
             }
         }
         c1 = wave_sum(c1) / cols;
@@ -261,7 +328,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const bf16* dy, const v
                 float* dst = dres + (long)row * lddres + idx * 4;
                 f32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = rs * (g[j][e] - c1 - xh[j][e] * c2);
+                for (int e = 0; e < 4; ++e) o[e] = ln_bwd_dx(g[j][e], xh[j][e], c1, c2, rs);
                 if (accumulate) {
                     const f32x4 old = *(const f32x4*)dst;
 #pragma unroll
@@ -279,7 +346,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const bf16* dy, const v
             }
         }
     }
-    // block reduction of the per-wave dgamma / dbeta partials, then one atomic per column per block
+    // block reduction of the per-wave dgamma / dbeta partials, then one float64 share per column per block (ln_bwd_put_sums)
     float* r0 = red;
     float* r1 = red + NW * 512;
     float* r2 = red + 2 * NW * 512;
@@ -300,12 +367,10 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const bf16* dy, const v
         }
         __syncthreads();
         for (int cidx = threadIdx.x; cidx < 512 && base + cidx < cols; cidx += NW * 64) {
-            float sg = 0.f, sb = 0.f, sc = 0.f;
+            double sg = 0., sb = 0., sc = 0.;
 #pragma unroll
             for (int w = 0; w < NW; ++w) { sg += r0[w * 512 + cidx]; sb += r1[w * 512 + cidx]; sc += r2[w * 512 + cidx]; }
-            atomicAdd(dgamma + base + cidx, sg);
-            atomicAdd(dbeta + base + cidx, sb);
-            if (dres_colsum) atomicAdd(dres_colsum + base + cidx, sc);
+            ln_bwd_put_sums(sums, dres_colsum != nullptr, cols, base + cidx, sg, sb, sc);
         }
         __syncthreads();
     }
@@ -317,9 +382,9 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const bf16* dy, const v
 template <bool XBF, int NV, int NW>
 __global__ __launch_bounds__(NW * 64) void ln_bwd_pf_kernel(const bf16* dy, const void* x, const float* mean,
                                                          const float* rstd, const float* gamma, float* dres,
-                                                         int accumulate, float* dgamma, float* dbeta, bf16* dres_lowp,
+                                                         int accumulate, bf16* dres_lowp,
                                                          float* dres_colsum, int rows, int cols, long lddy, long ldx, long lddres,
-                                                         long ldlowp) {
+                                                         long ldlowp, double* sums) {
     __shared__ float red[3 * NW * 512];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -371,14 +436,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_pf_kernel(const bf16* dy, cons
             const int idx = lane + 64 * j;
             if (idx < nvec) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xh[j][e] = (xv[j][e] - mu) * rs;
-                    g[j][e] = dv[j][e] * gm[j][e];
-                    c1 += g[j][e];
-                    c2 += g[j][e] * xh[j][e];
-                    ag[j][e] += dv[j][e] * xh[j][e];
-                    ab[j][e] += dv[j][e];
-                }
+                for (int e = 0; e < 4; ++e) LN_BWD_TERMS(xv[j][e], dv[j][e]);
             }
         }
         c1 = wave_sum(c1) / cols;
@@ -390,7 +448,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_pf_kernel(const bf16* dy, cons
                 float* dst = dres + (long)row * lddres + idx * 4;
                 f32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = rs * (g[j][e] - c1 - xh[j][e] * c2);
+                for (int e = 0; e < 4; ++e) o[e] = ln_bwd_dx(g[j][e], xh[j][e], c1, c2, rs);
                 if (accumulate) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] += old[j][e];
@@ -427,12 +485,10 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_pf_kernel(const bf16* dy, cons
         }
         __syncthreads();
         for (int cidx = threadIdx.x; cidx < 512 && base + cidx < cols; cidx += NW * 64) {
-            float sg = 0.f, sb = 0.f, sc = 0.f;
+            double sg = 0., sb = 0., sc = 0.;
 #pragma unroll
             for (int w = 0; w < NW; ++w) { sg += r0[w * 512 + cidx]; sb += r1[w * 512 + cidx]; sc += r2[w * 512 + cidx]; }
-            atomicAdd(dgamma + base + cidx, sg);
-            atomicAdd(dbeta + base + cidx, sb);
-            if (dres_colsum) atomicAdd(dres_colsum + base + cidx, sc);
+            ln_bwd_put_sums(sums, dres_colsum != nullptr, cols, base + cidx, sg, sb, sc);
         }
         __syncthreads();
     }
@@ -461,13 +517,21 @@ extern "C" int dw_layernorm_fwd_ld(const void* x, int x_dtype, const float* gamm
     if ((mean == nullptr) != (rstd == nullptr)) return DW_EINVAL;
     dim3 grid((rows + 3) / 4), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == DW_BF16 && (cols & 7) == 0 && ((ldx | ldy) & 7) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 &&
+    if (x_dtype == DW_BF16 && (cols & 7) == 0 && ((uintptr_t)x & 7) == 0 && ((uintptr_t)y & 7) == 0 &&
         ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0) {
         const int nv8 = ((cols >> 3) + 63) / 64;
-        if (nv8 <= 1) hipLaunchKernelGGL((ln_fwd_bf16x8_kernel<1>), grid, block, 0, s, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, rows, cols, eps, ldx, ldy);
-        else if (nv8 <= 2) hipLaunchKernelGGL((ln_fwd_bf16x8_kernel<2>), grid, block, 0, s, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, rows, cols, eps, ldx, ldy);
-        else if (nv8 <= 3) hipLaunchKernelGGL((ln_fwd_bf16x8_kernel<3>), grid, block, 0, s, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, rows, cols, eps, ldx, ldy);
-        else hipLaunchKernelGGL((ln_fwd_bf16x8_kernel<4>), grid, block, 0, s, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, rows, cols, eps, ldx, ldy);
+        const bool a16 = ((ldx | ldy) & 7) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0;
+#define LN_FWD8(NVV)                                                                                                  \
+    do {                                                                                                              \
+        if (a16)                                                                                                      \
+            hipLaunchKernelGGL((ln_fwd_bf16x8_kernel<NVV, true>), grid, block, 0, s, (const bf16*)x, gamma, beta,     \
+                               (bf16*)y, mean, rstd, rows, cols, eps, ldx, ldy);                                      \
+        else                                                                                                          \
+            hipLaunchKernelGGL((ln_fwd_bf16x8_kernel<NVV, false>), grid, block, 0, s, (const bf16*)x, gamma, beta,    \
+                               (bf16*)y, mean, rstd, rows, cols, eps, ldx, ldy);                                      \
+    } while (0)
+        if (nv8 <= 1) LN_FWD8(1); else if (nv8 <= 2) LN_FWD8(2); else if (nv8 <= 3) LN_FWD8(3); else LN_FWD8(4);
+#undef LN_FWD8
         DW_CHECK_LAUNCH();
         return DW_OK;
     }
@@ -494,63 +558,79 @@ extern "C" int dw_layernorm_fwd_ld(const void* x, int x_dtype, const float* gamm
     return DW_OK;
 }
 
+// Workgroups of the backward: exactly those that are resident at once (below), at most one per NW rows
+static int ln_bwd_blocks(int rows, int cols, int* nw_out) {
+    const int nv = ((cols >> 2) + 63) / 64;
+    const bool pf = (g_ln_variant & 2) && nv == 5;
+    const int nw = pf ? 8 : nv == 4 || nv == 5 ? 12 : 4;
+    const int resident = pf ? 256 : 256 * ((nv <= 3 ? 16 : nv <= 5 ? 12 : 4) / nw);
+    const int nb = (rows + nw - 1) / nw;
+    if (nw_out) *nw_out = nw;
+    return nb < resident ? nb : resident;
+}
+// Bytes of the `sums` workspace of dw_layernorm_bwd[_ld] for this shape (whatever key 21 says); 0 for a shape it rejects
+extern "C" int dw_layernorm_bwd_ws_bytes(int rows, int cols) {
+    if (rows <= 0 || cols <= 0 || (cols & 3) || cols > LN_MAXV * 256) return 0;
+    const int nv = ((cols >> 2) + 63) / 64;
+    int nb = (rows + (nv == 5 ? 7 : nv == 4 ? 11 : 3)) / (nv == 5 ? 8 : nv == 4 ? 12 : 4);
+    const int resident = nv <= 3 ? 1024 : 256;
+    if (nb > resident) nb = resident;
+    return (int)(3l * nb * cols * sizeof(double));
+}
+
 extern "C" int dw_layernorm_bwd_ld(const void* dy, const void* x, int x_dtype, const float* mean, const float* rstd,
                                    const float* gamma, float* dres, int accumulate, float* dgamma, float* dbeta,
                                    void* dres_lowp, float* dres_colsum, int rows, int cols, int64_t lddy_, int64_t ldx_,
-                                   int64_t lddres_, int64_t ldlowp_, void* stream);
+                                   int64_t lddres_, int64_t ldlowp_, void* sums, int64_t sums_bytes, void* stream);
 extern "C" int dw_layernorm_bwd(const void* dy, const void* x, int x_dtype, const float* mean, const float* rstd,
                                 const float* gamma, float* dres, int accumulate, float* dgamma, float* dbeta,
-                                void* dres_lowp, float* dres_colsum, int rows, int cols, void* stream) {
+                                void* dres_lowp, float* dres_colsum, int rows, int cols, void* sums, int64_t sums_bytes,
+                                void* stream) {
     return dw_layernorm_bwd_ld(dy, x, x_dtype, mean, rstd, gamma, dres, accumulate, dgamma, dbeta, dres_lowp, dres_colsum, rows,
-                               cols, cols, cols, cols, cols, stream);
+                               cols, cols, cols, cols, cols, sums, sums_bytes, stream);
 }
 // ... with row pitches (elements) of dy, x, the fp32 residual gradient and its bf16 copy
 extern "C" int dw_layernorm_bwd_ld(const void* dy, const void* x, int x_dtype, const float* mean, const float* rstd,
                                    const float* gamma, float* dres, int accumulate, float* dgamma, float* dbeta,
                                    void* dres_lowp, float* dres_colsum, int rows, int cols, int64_t lddy_, int64_t ldx_,
-                                   int64_t lddres_, int64_t ldlowp_, void* stream) {
+                                   int64_t lddres_, int64_t ldlowp_, void* sums_, int64_t sums_bytes, void* stream) {
     DW_CLEAR_ERR();
     if (!dy || !x || !mean || !rstd || !gamma || !dres || !dgamma || !dbeta) return DW_EINVAL;
     if (rows <= 0 || cols <= 0 || (cols & 3) || cols > LN_MAXV * 256) return DW_EINVAL;
     if (lddy_ < cols || ldx_ < cols || lddres_ < cols || ldlowp_ < cols || ((lddy_ | ldx_ | lddres_ | ldlowp_) & 3)) return DW_EINVAL;
+    int nw = 0;
+    const int nb = ln_bwd_blocks(rows, cols, &nw);
+    if (!sums_ || ((uintptr_t)sums_ & 7) || sums_bytes < (int64_t)(3l * nb * cols * sizeof(double))) return DW_EINVAL;
+    double* sums = (double*)sums_;
     const long lddy = lddy_, ldx = ldx_, lddres = lddres_, ldlowp = ldlowp_;
     hipStream_t s = (hipStream_t)stream;
     const int nv = ((cols >> 2) + 63) / 64;
     // grid = exactly the workgroups that are resident at once: a grid-stride loop over rows on a grid of 1.33 rounds left
     // a third of the chip idle in the tail.  Registers allow 16 / 12 / 4 waves per CU for <=3 / 5 / 8 vectors per lane; at 5
-    // (cols = 1280) the twelve waves are ONE workgroup, so that a CU issues a third of the dgamma / dbeta / column-sum
-    // atomics of four-wave workgroups: the atomics are rate-limited (2.9 M of them were 21 us of a 248 us launch; measured
-    // with them switched off), 249 -> 238 us.  Requesting the residual gradient with the other operands instead of after the
-    // reductions costs a wave per SIMD in registers and is slower (279 us), and so are LDS accumulators (ds_add_f32: 948 us)
-    // and one lane per column segment with the row statistics exchanged through LDS (295 us).
-#define LN_BWD(NVV, NWW)                                                                                              \
+    // (cols = 1280) the twelve waves are ONE workgroup: a third of the column-sum shares of four-wave workgroups.
+    // Requesting the residual gradient with the other operands instead of after the reductions costs a wave per SIMD in
+    // registers and is slower (279 us), and so are LDS accumulators (ds_add_f32: 948 us) and one lane per column segment with
+    // the row statistics exchanged through LDS (295 us).
+#define LN_BWD(KERNEL, NVV, NWW)                                                                                      \
     do {                                                                                                              \
-        int nb = (rows + NWW - 1) / NWW;                                                                              \
-        const int resident = 256 * ((NVV <= 3 ? 16 : NVV <= 5 ? 12 : 4) / NWW);                                       \
-        if (nb > resident) nb = resident;                                                                             \
         if (x_dtype == DW_BF16)                                                                                       \
-            hipLaunchKernelGGL((ln_bwd_kernel<true, NVV, NWW>), dim3(nb), dim3(NWW * 64), 0, s, (const bf16*)dy, x,   \
-                               mean, rstd, gamma, dres, accumulate, dgamma, dbeta, (bf16*)dres_lowp, dres_colsum,     \
-                               rows, cols, lddy, ldx, lddres, ldlowp);                                                                           \
+            hipLaunchKernelGGL((KERNEL<true, NVV, NWW>), dim3(nb), dim3(NWW * 64), 0, s, (const bf16*)dy, x, mean,    \
+                               rstd, gamma, dres, accumulate, (bf16*)dres_lowp, dres_colsum, rows, cols, lddy, ldx,   \
+                               lddres, ldlowp, sums);                                                                 \
         else                                                                                                          \
-            hipLaunchKernelGGL((ln_bwd_kernel<false, NVV, NWW>), dim3(nb), dim3(NWW * 64), 0, s, (const bf16*)dy, x,  \
-                               mean, rstd, gamma, dres, accumulate, dgamma, dbeta, (bf16*)dres_lowp, dres_colsum,     \
-                               rows, cols, lddy, ldx, lddres, ldlowp);                                                                           \
+            hipLaunchKernelGGL((KERNEL<false, NVV, NWW>), dim3(nb), dim3(NWW * 64), 0, s, (const bf16*)dy, x, mean,   \
+                               rstd, gamma, dres, accumulate, (bf16*)dres_lowp, dres_colsum, rows, cols, lddy, ldx,   \
+                               lddres, ldlowp, sums);                                                                 \
     } while (0)
-    if ((g_ln_variant & 2) && nv == 5) {
-        int nb = (rows + 7) / 8;
-        if (nb > 256) nb = 256;
-        if (x_dtype == DW_BF16)
-            hipLaunchKernelGGL((ln_bwd_pf_kernel<true, 5, 8>), dim3(nb), dim3(512), 0, s, (const bf16*)dy, x, mean, rstd, gamma, dres,
-                               accumulate, dgamma, dbeta, (bf16*)dres_lowp, dres_colsum, rows, cols, lddy, ldx, lddres, ldlowp);
-        else
-            hipLaunchKernelGGL((ln_bwd_pf_kernel<false, 5, 8>), dim3(nb), dim3(512), 0, s, (const bf16*)dy, x, mean, rstd, gamma, dres,
-                               accumulate, dgamma, dbeta, (bf16*)dres_lowp, dres_colsum, rows, cols, lddy, ldx, lddres, ldlowp);
-        DW_CHECK_LAUNCH();
-        return DW_OK;
-    }
-    if (nv <= 2) LN_BWD(2, 4); else if (nv <= 3) LN_BWD(3, 4); else if (nv <= 5) LN_BWD(5, 12); else LN_BWD(8, 4);
+    if (nw == 8) LN_BWD(ln_bwd_pf_kernel, 5, 8);
+    else if (nv <= 2) LN_BWD(ln_bwd_kernel, 2, 4);
+    else if (nv <= 3) LN_BWD(ln_bwd_kernel, 3, 4);
+    else if (nv <= 5) LN_BWD(ln_bwd_kernel, 5, 12);
+    else LN_BWD(ln_bwd_kernel, 8, 4);
 #undef LN_BWD
+    DW_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ln_bwd_sums_kernel, dim3((cols + 63) / 64, 3), dim3(1024), 0, s, (const double*)sums, nb, dgamma, dbeta,
+                       dres_colsum, cols);
     DW_CHECK_LAUNCH();
     return DW_OK;
 }

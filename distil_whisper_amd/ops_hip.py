@@ -60,12 +60,13 @@ _SIGS = {
     "dw_layernorm_fwd": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                           C.c_int, C.c_float, C.c_void_p], C.c_int),
     "dw_layernorm_bwd": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p], C.c_int),
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "dw_layernorm_bwd_ws_bytes": ([C.c_int, C.c_int], C.c_int),
     "dw_reduce_slices_ld": ([C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "dw_layernorm_fwd_ld": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                              C.c_int, C.c_float, C.c_int64, C.c_int64, C.c_void_p], C.c_int),
     "dw_layernorm_bwd_ld": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_int64] * 4 + [C.c_void_p], C.c_int),
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_int64] * 4 + [C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "dw_attn_fwd": ([C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_int64] * 4 + [C.c_int, C.c_float, C.c_void_p], C.c_int),
     "dw_attn_fwd_ex": ([C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_int64] * 6 + [C.c_int, C.c_float, C.c_void_p], C.c_int),
     "dw_attn_fwd_varlen": ([C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_int64] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_int, C.c_float,
@@ -431,9 +432,12 @@ class HipOps:
             assert out_lowp.dtype == torch.bfloat16 and out_lowp.stride(1) == 1 and out_lowp.shape == (rows, cols)
             ldl = out_lowp.stride(0)
         assert colsum is None or out_lowp is not None
+        # the kernels' float64 shares of the column sums: the caching allocator keeps the block until the stream has passed it
+        sums = self.empty((self.lib.dw_layernorm_bwd_ws_bytes(rows, cols) // 8,), torch.float64)
         self._chk(self.lib.dw_layernorm_bwd_ld(_p(dy), _p(x), _dt(x), _p(mean), _p(rstd), _p(gamma), _p(dres), int(acc),
                                                _p(dgamma), _p(dbeta), _p(out_lowp), _p(colsum), rows, cols,
-                                               dy.stride(0), x.stride(0), dres.stride(0), ldl, self._stream()), "layernorm_bwd")
+                                               dy.stride(0), x.stride(0), dres.stride(0), ldl, _p(sums), sums.numel() * 8,
+                                               self._stream()), "layernorm_bwd")
         return dres
 
     def attn_fwd_varlen(self, q, k, v, H, max_q, q_start, q_len, causal, scale, out, Lk=0, kv_batches=0, self_attention=True,
@@ -504,10 +508,11 @@ class HipOps:
         return dq, dk, dv
 
     def distill_loss(self, s_logits, t_logits, labels, V, temperature, ce_weight, kl_weight, grad_scale, want_grad,
-                     grad_out=None, weights_dev=None):
+                     grad_out=None, weights_dev=None, return_rows=False):
         """Returns losses f32[4] = (ce, kl, total, n_valid).  With want_grad the gradient w.r.t. the student logits
         overwrites s_logits in place (bf16), or goes to `grad_out` (same shape and dtype) when that is given.
-        `weights_dev` (f32[2] on the device) replaces (ce_weight, kl_weight): dw_distill_loss_w."""
+        `weights_dev` (f32[2] on the device) replaces (ce_weight, kl_weight): dw_distill_loss_w.
+        return_rows: -> (losses, row_ce, row_kl), the kernel's per-row terms f32[rows] (0 in the rows its label excludes)."""
         rows, ld = s_logits.shape
         if grad_out is not None:
             assert want_grad and grad_out.shape == s_logits.shape and grad_out.dtype == torch.bfloat16 and grad_out.is_contiguous()
@@ -524,12 +529,12 @@ class HipOps:
             self._chk(self.lib.dw_distill_loss_w(_p(s_logits), _p(t_logits), _p(labels), rows, V, ld, float(temperature),
                                                  _p(weights_dev), float(grad_scale), _p(losses), dl, _p(row_ce), _p(row_kl),
                                                  _p(counts), self._stream()), "distill_loss_w")
-            return losses
+            return (losses, row_ce, row_kl) if return_rows else losses
         self._chk(self.lib.dw_distill_loss(_p(s_logits), _p(t_logits), _p(labels), rows, V, ld, float(temperature),
                                            float(ce_weight), float(kl_weight), float(grad_scale), _p(losses), dl,
                                            _p(row_ce), _p(row_kl), _p(counts),
                                            self._stream()), "distill_loss")
-        return losses
+        return (losses, row_ce, row_kl) if return_rows else losses
 
     def embed_fwd(self, ids, tok, pos, out_dtype, rows_alloc=0):
         """rows_alloc > B*T: the output buffer gets that many rows (the extra rows are zero; callers whose GEMMs run

@@ -111,12 +111,15 @@ int dw_reduce_slices_ld(const float* part, int64_t slice_stride, int64_t ld_part
 int dw_layernorm_fwd(const void* x, int x_dtype, const float* gamma, const float* beta, void* y, float* mean,
                      float* rstd, int rows, int cols, float eps, void* stream);
 /* dx = LN'(dy); if accumulate: dres[rows][cols] (f32) += dx else dres = dx.  dgamma/dbeta f32 [cols] are ADDED to
- * (atomics; zero them first).  Optional fused outputs: dres_lowp (bf16 [rows][cols]) = bf16(dres) -- the gradient the
+ * (zero them first).  Optional fused outputs: dres_lowp (bf16 [rows][cols]) = bf16(dres) -- the gradient the
  * next residual branch's GEMMs consume -- and dres_colsum (f32 [cols], ADDED to) = its column sums = the bias gradient
- * of that branch's output projection. */
+ * of that branch's output projection.  The three column sums are taken in float64 in a fixed order (the same inputs give
+ * the same bits) through `sums`: caller-owned, 8-byte aligned, at least dw_layernorm_bwd_ws_bytes(rows, cols) bytes, any
+ * content; it must stay untouched until the work queued on `stream` has run. */
+int dw_layernorm_bwd_ws_bytes(int rows, int cols);
 int dw_layernorm_bwd(const void* dy_bf16, const void* x, int x_dtype, const float* mean, const float* rstd,
                      const float* gamma, float* dres, int accumulate, float* dgamma, float* dbeta, void* dres_lowp,
-                     float* dres_colsum, int rows, int cols, void* stream);
+                     float* dres_colsum, int rows, int cols, void* sums, int64_t sums_bytes, void* stream);
 /* The same two with row pitches in elements (>= cols, multiples of 4; 8 for bf16 x): activation buffers whose rows are padded
  * by 128 bytes so that the 128-byte pieces a GEMM tile reads from 256-320 consecutive rows do not fall on two of an XCD's sixteen
  * L2 channels (rows 2 560 / 10 240 bytes apart do; engine.row_pad, tools/gemm_stride_probe.py). */
@@ -125,7 +128,7 @@ int dw_layernorm_fwd_ld(const void* x, int x_dtype, const float* gamma, const fl
 int dw_layernorm_bwd_ld(const void* dy_bf16, const void* x, int x_dtype, const float* mean, const float* rstd,
                         const float* gamma, float* dres, int accumulate, float* dgamma, float* dbeta, void* dres_lowp,
                         float* dres_colsum, int rows, int cols, int64_t lddy, int64_t ldx, int64_t lddres,
-                        int64_t ldlowp, void* stream);
+                        int64_t ldlowp, void* sums, int64_t sums_bytes, void* stream);
 
 /* ---- attention core (TF:modeling_whisper.py:215-238 / integrations/sdpa_attention.py), head_dim 64 --------------
  * q [B*Lq rows], k,v [B*Lk rows]: bf16, head h of a row at element offset h*64, row strides ldq/ldk/ldv/ldo

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import attention_restatement as ar
+from guarded import Guarded, Guarded32
 
 pytestmark = pytest.mark.gpu
 
@@ -55,42 +56,6 @@ def debug(ops, key, value):
 def relerr(a, b):
     a, b = a.double(), b.double()
     return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-class Guarded:
-    """A [rows, cols] bf16 output inside a larger NaN-patterned buffer: `pad` extra columns per row, the live columns starting at
-    column `off`, guard rows behind.  intact(): every element outside the live view still holds the pattern, bit for bit."""
-
-    def __init__(self, rows, cols, pad=8, off=0, guard_rows=3):
-        self.buf = torch.empty(rows + guard_rows, cols + pad, dtype=torch.bfloat16, device=DEV)
-        self.buf.view(torch.int16).fill_(ar.NAN16)
-        self.rows, self.cols, self.off = rows, cols, off
-        self.live = self.buf[:rows, off:off + cols]
-
-    def intact(self):
-        g = self.buf.view(torch.int16).clone()
-        g[:self.rows, self.off:self.off + self.cols] = ar.NAN16
-        return bool((g == ar.NAN16).all())
-
-    def untouched(self):
-        return bool((self.buf.view(torch.int16) == ar.NAN16).all())
-
-
-class Guarded32:
-    """n live floats with `guard` patterned slots behind them."""
-
-    def __init__(self, n, guard=16, zero=False):
-        self.buf = torch.empty(n + guard, dtype=torch.float32, device=DEV)
-        self.buf.view(torch.int32).fill_(ar.NAN32)
-        self.live = self.buf[:n]
-        if zero:
-            self.live.zero_()
-
-    def intact(self):
-        return bool((self.buf[self.live.numel():].view(torch.int32) == ar.NAN32).all())
-
-    def untouched(self):
-        return bool((self.buf.view(torch.int32) == ar.NAN32).all())
 
 
 def fwd(ops, q, k, v, o, lse, B, H, Lq, Lk, causal, kv_batch_rows=None):
