@@ -44,8 +44,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_kernel.h"), os.path.join(CSRC, "gemm_wp.h"), os.path.join(CSRC, "gemm_wp16.h"), os.path.join(CSRC, "select_rules.h"),
                os.path.join(HERE, "..", "include", "dwamd.h")]
     objs, procs = [], []
-    flags = FLAGS + (["-DDW_ABLATE"] if os.environ.get("DW_ABLATE") else [])   # timing-experiment kernels (tools/attn_ablate.py)
-    flags += os.environ.get("DW_EXTRA_FLAGS", "").split()                      # -D switches of A/B builds (tools/build_variant_lib.sh)
+    flags = FLAGS + os.environ.get("DW_EXTRA_FLAGS", "").split()               # -D switches of A/B builds (tools/build_variant_lib.sh)
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))

@@ -20,9 +20,6 @@
 #ifndef DW_ATTN_DEFER
 #define DW_ATTN_DEFER 8
 #endif
-#ifndef DW_ATTN_IDLE_SKIP
-#define DW_ATTN_IDLE_SKIP 1   // a wave whose 32 stationary rows lie wholly behind the end of the sequence skips its tiles' arithmetic
-#endif
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 struct AttnP {
@@ -64,11 +61,7 @@ __device__ __forceinline__ void store_t(bf16* base, long ld, long row, bool ok, 
         bf16x4 w;
 #pragma unroll
         for (int e = 0; e < 4; ++e) w[e] = f2bf(a[g * 4 + e] * mul);
-#ifdef DW_NT_ATTN
-        __builtin_nontemporal_store(w, (bf16x4*)(base + row * ld + cb * 32 + g * 8 + hi * 4));
-#else
         *(bf16x4*)(base + row * ld + cb * 32 + g * 8 + hi * 4) = w;
-#endif
     }
 }
 
@@ -77,9 +70,6 @@ __device__ __forceinline__ void store_t(bf16* base, long ld, long row, bool ok, 
 // LDS, a store instruction writes 8 complete 128-byte rows (16 bytes per lane).  Without any output store the kernels run
 // 5 % (encoder shape) to 13 % (cross-attention backward) faster -- the row-per-lane stores were most of that (section 14).
 // `patch`: this wave's 4608 bytes; the caller has made sure that no wave still reads the operand tiles it overlays.
-#ifndef DW_ATTN_ROWSTORE
-#define DW_ATTN_ROWSTORE 1
-#endif
 __device__ __forceinline__ void store_rows(bf16* base, long ld, int row0, int nrows, char* patch, int lane,
                                            const f32x16& a0, const f32x16& a1, float mul) {
     const int hi = lane >> 5, ln = lane & 31;
@@ -138,11 +128,9 @@ __device__ __forceinline__ void attn_workgroup(int ntile, int H, bool plain, int
 // ---------------------------------------------------------------------------------------------------------------
 // forward: block = NW waves x 32 queries; key/value tiles of 64 rows double-buffered in LDS
 // ---------------------------------------------------------------------------------------------------------------
-// ABL (builds with -DDW_ABLATE only, tools/attn_ablate.py): timing experiments that leave out one resource user each and
-// compute garbage -- 1 no exp, 2 / 4 K / V fragments from registers instead of LDS, 8 no operand staging inside the loop,
-// 16 no barrier, 32 / 64 without the QK / PV MFMAs.
-template <bool CAUSAL, int NW = 4, int ABL = 0, bool VL = false>
-__global__ __launch_bounds__(64 * NW, CAUSAL ? 2 : 4) void attn_fwd_kernel(const AttnP p) {
+template <bool CAUSAL, bool VL = false>
+__global__ __launch_bounds__(256, CAUSAL ? 2 : 4) void attn_fwd_kernel(const AttnP p) {
+    constexpr int NW = 4;   // waves per workgroup
     __shared__ __attribute__((aligned(1024))) char smem[2 * 16384];  // [buf][K tile 8K | V tile 8K]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -189,28 +177,24 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 2 : 4) void attn_fwd_kernel(const
     stage_tile64<NW>(V, p.ldv, 0, Lk, smem + 8192, wave, lane);
     for (int kt = 0; kt < nkt; ++kt) {
         const int buf = kt & 1;
-        if (!(ABL & 16) || kt == 0) {
-            wait_vm0_seen();    // (seen by the compiler: its counted waits for the Q fragment loads otherwise sit inside this loop)
-            __syncthreads();
-        }
-        if (kt + 1 < nkt && !(ABL & 8)) {
+        wait_vm0_seen();    // (seen by the compiler: its counted waits for the Q fragment loads otherwise sit inside this loop)
+        __syncthreads();
+        if (kt + 1 < nkt) {
             stage_tile64<NW>(K, p.ldk, (kt + 1) * 64, Lk, smem + (buf ^ 1) * 16384, wave, lane);
             stage_tile64<NW>(V, p.ldv, (kt + 1) * 64, Lk, smem + (buf ^ 1) * 16384 + 8192, wave, lane);
         }
         const char* tK = smem + buf * 16384;
         const char* tV = tK + 8192;
-        if (DW_ATTN_IDLE_SKIP && qb0 + wave * 32 >= Lq) continue;   // none of this wave's 32 queries exists (the last wave of the
-                                                                      // 1500-query tail workgroup): it stages and meets the barriers only
+        if (qb0 + wave * 32 >= Lq) continue;   // none of this wave's 32 queries exists (the last wave of the 1500-query tail
+                                               // workgroup): it stages and meets the barriers only, and skips the tile's arithmetic
         f32x16 s[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) s[kb][r] = (ABL & 32) ? o[kb][r] : 0.f;
-            if (!(ABL & 32)) {
+            for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-                    s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16((ABL & 2) ? qf[kk ^ kb] : frag_rows(tK, kb, kk, lane), qf[kk], s[kb], 0, 0, 0);
-            }
+            for (int kk = 0; kk < 4; ++kk)
+                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(tK, kb, kk, lane), qf[kk], s[kb], 0, 0, 0);
         }
         // mask (key tail / causal diagonal) only on the tiles that need it -- a wave-uniform test
         const int wq0 = qb0 + wave * 32 + (CAUSAL ? p.coff : 0);   // last key the wave's first query may see
@@ -249,8 +233,7 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 2 : 4) void attn_fwd_kernel(const
             for (int r = 0; r < 16; r += 2) {
                 f32x2 t = {s[kb][r], s[kb][r + 1]};
                 t = t * c2 - mc2;
-                f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-                if (ABL & 1) pv = t;
+                const f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
                 s[kb][r] = pv[0];
                 s[kb][r + 1] = pv[1];
                 rs2[(r >> 1) & 1] += pv;
@@ -273,18 +256,14 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 2 : 4) void attn_fwd_kernel(const
             for (int s2 = 0; s2 < 2; ++s2) {
                 const bf16x8 pf = pack8(s[kb], s2);
                 const int rb = kb * 32 + s2 * 16 + hi * 4;
-                if (ABL & 64) {
-                    o[kb][s2] += bf2f(pf[0]) + bf2f(pf[2]) + bf2f(pf[4]) + bf2f(pf[6]);
-                    continue;
-                }
 #pragma unroll
                 for (int db = 0; db < 2; ++db)
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16((ABL & 4) ? qf[db * 2 + s2] : frag_tr(tV, db, rb, rb + 8, lane), pf, o[db], 0, 0, 0);
+                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(tV, db, rb, rb + 8, lane), pf, o[db], 0, 0, 0);
             }
     }
     const float inv = 1.0f / l_run;
     bf16* O = p.o + q_row0 * p.ldo + h * 64;
-    if (DW_ATTN_ROWSTORE && NW <= 7 && (p.ldo & 7) == 0 && ((uintptr_t)p.o & 15) == 0) {
+    if ((p.ldo & 7) == 0 && ((uintptr_t)p.o & 15) == 0) {
         __syncthreads();                              // every wave is done with the last K/V tile: the patches overlay the tiles
         store_rows(O, p.ldo, qb0 + wave * 32, Lq, smem + wave * 4608, lane, o[0], o[1], inv);
     } else {
@@ -292,148 +271,6 @@ __global__ __launch_bounds__(64 * NW, CAUSAL ? 2 : 4) void attn_fwd_kernel(const
         store_t(O, p.ldo, q, q_ok, 1, hi, o[1], inv);
     }
     if (!VL && p.lse && q_ok && hi == 0) p.lse[((long)b * p.H + h) * Lq + q] = m_run * p.scale + __logf(l_run);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// forward, software-pipelined across key tiles (non-causal shapes; dw_debug_set key 26).  In attn_fwd_kernel a wave runs
-// QK(t) -> softmax(t) -> PV(t) strictly in sequence: the softmax's ~100 vector instructions wait for the QK MFMAs to drain and the
-// PV MFMAs for the softmax, and only the other waves of the SIMD fill the holes.  Here the scores of tile t+1 are computed one
-// iteration ahead (two score register sets, ping-pong by name): inside an iteration the QK MFMAs of tile t+1 and the softmax of
-// tile t are independent instruction streams of the SAME wave -- the matrix pipe works on one while the vector unit works on the
-// other.  Costs: 32 more registers (three waves per SIMD instead of four) and a THIRD K / V stage in LDS (tile t+1 must be
-// resident while tile t is still read by the PV product): 48 KiB per workgroup, three workgroups per CU.
-// Same arithmetic per element and the same order of every sum as attn_fwd_kernel: bit-identical output.
-// ---------------------------------------------------------------------------------------------------------------
-template <int NW = 4, int OCC = 3>
-__global__ __launch_bounds__(64 * NW, OCC) void attn_fwd_pipe_kernel(const AttnP p) {
-    __shared__ __attribute__((aligned(1024))) char smem[3 * 16384];  // [stage][K tile 8K | V tile 8K]
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int hi = lane >> 5, ln = lane & 31;
-    int tile, h, b;
-    attn_workgroup((p.Lq + 32 * NW - 1) / (32 * NW), p.H, p.plain_order, tile, h, b);
-    const int qb0 = tile * (32 * NW);
-    const int q = qb0 + wave * 32 + ln;
-    const bool q_ok = q < p.Lq;
-    const int qc = q_ok ? q : p.Lq - 1;
-    const bf16* Q = p.q + (long)b * p.q_rows * p.ldq + h * 64;
-    const bf16* K = p.k + (long)b * p.kv_rows * p.ldk + h * 64;
-    const bf16* V = p.v + (long)b * p.kv_rows * p.ldv + h * 64;
-    bf16x8 qf[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) qf[kk] = ldg8(Q, qc, p.ldq, kk * 16 + hi * 8);
-    const int nkt = (p.Lk + 63) >> 6;
-    const float c = p.scale * 1.4426950408889634f;
-    float m_run = NEG_BIG, l_run = 0.f;
-    f32x16 o[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
-
-    auto stage = [&](int kt, int st) __attribute__((always_inline)) {
-        stage_tile64<NW>(K, p.ldk, kt * 64, p.Lk, smem + st * 16384, wave, lane);
-        stage_tile64<NW>(V, p.ldv, kt * 64, p.Lk, smem + st * 16384 + 8192, wave, lane);
-    };
-    // S^T of key tile kt (stage st), masked on the tail tile
-    auto scores = [&](int kt, int st, f32x16 (&s)[2]) __attribute__((always_inline)) {
-        const char* tK = smem + st * 16384;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(tK, kb, kk, lane), qf[kk], s[kb], 0, 0, 0);
-        }
-        if ((kt + 1) * 64 > p.Lk) {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    s[kb][r] = key < p.Lk ? s[kb][r] : NEG_BIG;
-                }
-        }
-    };
-    // softmax of one tile's scores (in place: s becomes P) + the PV product out of stage st
-    auto softmax_pv = [&](int st, f32x16 (&s)[2]) __attribute__((always_inline)) {
-        const char* tV = smem + st * 16384 + 8192;
-        float mx = NEG_BIG;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-        mx = xhalf_max(mx);
-        const bool move = __any((mx - m_run) * c > p.defer);
-        const float m_new = move ? fmaxf(m_run, mx) : m_run;
-        const float mc = m_new * c;
-        f32x2 rs2[2] = {{0.f, 0.f}, {0.f, 0.f}};
-        const f32x2 c2 = {c, c}, mc2 = {mc, mc};
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                f32x2 t = {s[kb][r], s[kb][r + 1]};
-                t = t * c2 - mc2;
-                const f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-                s[kb][r] = pv[0];
-                s[kb][r + 1] = pv[1];
-                rs2[(r >> 1) & 1] += pv;
-            }
-        rs2[0] += rs2[1];
-        float rs = rs2[0][0] + rs2[0][1];
-        rs = xhalf_sum(rs);
-        if (move) {
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-            l_run *= alpha;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
-        }
-        l_run += rs;
-        m_run = m_new;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 pf = pack8(s[kb], s2);
-                const int rb = kb * 32 + s2 * 16 + hi * 4;
-#pragma unroll
-                for (int db = 0; db < 2; ++db)
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(tV, db, rb, rb + 8, lane), pf, o[db], 0, 0, 0);
-            }
-    };
-
-    stage(0, 0);
-    if (nkt > 1) stage(1, 1);
-    wait_vm0_seen();
-    __syncthreads();
-    f32x16 sa[2], sb[2];
-    scores(0, 0, sa);
-    // iteration kt: tile kt's scores are in `cur`; tile kt in stage st0, tile kt+1 (requested an iteration ago) in st1
-    auto iter = [&](int kt, int st0, int st1, int st2, f32x16 (&cur)[2], f32x16 (&nxt)[2]) __attribute__((always_inline)) {
-        if (kt > 0) {                       // (iteration 0: tiles 0 and 1 were waited for in front of the loop)
-            wait_vm0_seen();                // tile kt+1 has landed ...
-            __syncthreads();                // ... for every wave, and every wave is done with tile kt-1 (stage st2)
-        }
-        if (kt + 2 < nkt) stage(kt + 2, st2);
-        if (kt + 1 < nkt) scores(kt + 1, st1, nxt);
-        softmax_pv(st0, cur);
-    };
-    int st0 = 0, st1 = 1, st2 = 2;
-    for (int kt = 0; kt < nkt; kt += 2) {
-        iter(kt, st0, st1, st2, sa, sb);
-        if (kt + 1 < nkt) iter(kt + 1, st1, st2, st0, sb, sa);
-        const int t0 = st0; st0 = st2; st2 = st1; st1 = t0;      // two tiles on: (st0, st1, st2) -> (st2, st0, st1)
-    }
-    const float inv = 1.0f / l_run;
-    bf16* O = p.o + (long)b * p.q_rows * p.ldo + h * 64;
-    if (DW_ATTN_ROWSTORE && (p.ldo & 7) == 0 && ((uintptr_t)p.o & 15) == 0) {
-        __syncthreads();
-        store_rows(O, p.ldo, qb0 + wave * 32, p.Lq, smem + wave * 4608, lane, o[0], o[1], inv);
-    } else {
-        store_t(O, p.ldo, q, q_ok, 0, hi, o[0], inv);
-        store_t(O, p.ldo, q, q_ok, 1, hi, o[1], inv);
-    }
-    if (p.lse && q_ok && hi == 0) p.lse[((long)b * p.H + h) * p.Lq + q] = m_run * p.scale + __logf(l_run);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -446,11 +283,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_fwd_pipe_kernel(const AttnP
 // wave partials meet through shuffles and LDS.  All (batch, head) workgroups are resident at once (320 for the
 // long-form batch of 16), unlike the 128-query tile kernel which would run 1.25 rounds of mostly idle tiles.
 // ---------------------------------------------------------------------------------------------------------------
-// PRE: every lane requests ALL its K and V chunks at kernel entry (Lk <= NW * 8 * 12 keys: 12 + 12 16-byte loads per
-// lane, 96 registers), so the whole K/V stream of the (batch, head) pair is in flight at once and the two passes run out
-// of registers -- the same idea as the weight-streaming GEMV; without it the second pass (V) cannot start its loads
-// before the maximum of the first pass is known.
-template <int NW, bool PRE>
+template <int NW>
 __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) float dsm[];   // [Lk scores | NW x 64 partial outputs | NW | NW]
     const int lane = threadIdx.x & 63;
@@ -471,39 +304,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(const AttnP p) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) qv[e] = bf2f(q8[e]) * c;
     }
-    constexpr int NIT = 12;
-    bf16x8 kr[PRE ? NIT : 1], vr[PRE ? NIT : 1];
-    if constexpr (PRE) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            int k = wave * 8 + it * (NW * 8) + sub;
-            k = k < p.Lk ? k : p.Lk - 1;
-            kr[it] = ld_stream<2>((const bf16x8*)(K + (long)k * p.ldk));
-        }
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            int k = wave * 8 + it * (NW * 8) + sub;
-            k = k < p.Lk ? k : p.Lk - 1;
-            vr[it] = ld_stream<2>((const bf16x8*)(V + (long)k * p.ldv));
-        }
-    }
     // ---- pass 1: scores (in log2 units) and their maximum ----
     float mx = NEG_BIG;
-    float sreg[PRE ? NIT : 1];
-    if constexpr (PRE) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int k = wave * 8 + it * (NW * 8) + sub;
-            float s = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s = fmaf(qv[e], bf2f(kr[it][e]), s);
-            s += __shfl_xor(s, 1);
-            s += __shfl_xor(s, 2);
-            s += __shfl_xor(s, 4);
-            sreg[it] = s;
-            if (k < p.Lk) mx = fmaxf(mx, s);
-        }
-    } else {
     for (int k0 = wave * 8; k0 < p.Lk; k0 += NW * 8) {
         const int k = k0 + sub;
         float s = 0.f;
@@ -520,7 +322,6 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(const AttnP p) {
             mx = fmaxf(mx, s);
         }
     }
-    }
     mx = wave_max(mx);
     if (lane == 0) redm[wave] = mx;
     __syncthreads();
@@ -530,19 +331,6 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(const AttnP p) {
     // ---- pass 2: probabilities, normaliser and the weighted sum of V ----
     float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float l = 0.f;
-    if constexpr (PRE) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int k = wave * 8 + it * (NW * 8) + sub;
-            if (k < p.Lk) {
-                const float pv = __builtin_amdgcn_exp2f(sreg[it] - mx);
-                l += pv;
-                const float pb = round_bf16(pv);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = fmaf(pb, bf2f(vr[it][e]), o[e]);
-            }
-        }
-    } else {
     for (int k0 = wave * 8; k0 < p.Lk; k0 += NW * 8) {
         const int k = k0 + sub;
         if (k < p.Lk) {
@@ -553,7 +341,6 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(const AttnP p) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = fmaf(pb, bf2f(v8[e]), o[e]);
         }
-    }
     }
     // the 8 lanes of a key group hold the same l contribution: count it once (lane & 7 == 0), then reduce
     l = (lane & 7) == 0 ? l : 0.f;
@@ -585,8 +372,9 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(const AttnP p) {
 // backward dQ: stationary = 32 queries per wave (Q, dO fragments + lse, delta in registers); stream K, V tiles
 //   S^T = K.Q^T, dP^T = V.dO^T, dS^T = P^T*(dP^T - delta), dQ^T[d][q] += K^T . dS^T
 // ---------------------------------------------------------------------------------------------------------------
-template <bool CAUSAL, bool FS, int NW = 4>
-__global__ __launch_bounds__(64 * NW, 3) void attn_bwd_dq_kernel(const AttnP p) {
+template <bool CAUSAL>
+__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const AttnP p) {
+    constexpr int NW = 4;   // waves per workgroup
     __shared__ __attribute__((aligned(1024))) char smem[2 * 16384];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -639,8 +427,8 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_bwd_dq_kernel(const AttnP p) 
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
 
-    stage_tile64<NW, FS>(K, p.ldk, 0, p.Lk, smem, wave, lane);
-    stage_tile64<NW, FS>(V, p.ldv, 0, p.Lk, smem + 8192, wave, lane);
+    stage_tile64<NW>(K, p.ldk, 0, p.Lk, smem, wave, lane);
+    stage_tile64<NW>(V, p.ldv, 0, p.Lk, smem + 8192, wave, lane);
     // The tile loop exists per mask mode (0 none, 1 every pair, 2 decided per tile: the causal kernels) and the non-causal launch
     // runs the full key tiles through mode 0 and the last, partial one through mode 1: tested inside ONE unrolled body the
     // wave-uniform flag became sixteen taken branches per tile (round 5, from the generated code).
@@ -658,15 +446,15 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_bwd_dq_kernel(const AttnP p) 
         if (kt + 1 < nkt) {
             int lane_s = lane_o;           // (per iteration: hoisted out of the loop, the staging's lane offsets are what gets spilled)
             asm volatile("" : "+v"(lane_s));
-            stage_tile64<NW, FS>(K, p.ldk, (kt + 1) * 64, p.Lk, smem + (buf ^ 1) * 16384, wave, lane_s);
-            stage_tile64<NW, FS>(V, p.ldv, (kt + 1) * 64, p.Lk, smem + (buf ^ 1) * 16384 + 8192, wave, lane_s);
+            stage_tile64<NW>(K, p.ldk, (kt + 1) * 64, p.Lk, smem + (buf ^ 1) * 16384, wave, lane_s);
+            stage_tile64<NW>(V, p.ldv, (kt + 1) * 64, p.Lk, smem + (buf ^ 1) * 16384 + 8192, wave, lane_s);
         }
         const char* tK = smem + buf * 16384;
         const char* tV = tK + 8192;
         const int wq0 = qb0 + wave * 32;
         const bool need_mask = MODE == 1 || (MODE == 2 && (((kt + 1) * 64 > p.Lk) || (CAUSAL && kt * 64 + 63 > wq0)));
         if (CAUSAL && kt * 64 > wq0 + 31) continue;
-        if (DW_ATTN_IDLE_SKIP && wq0 >= p.Lq) continue;               // (see attn_fwd_kernel)
+        if (wq0 >= p.Lq) continue;                                    // (idle wave: see attn_fwd_kernel)
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             f32x16 s, dp;
@@ -713,7 +501,7 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_bwd_dq_kernel(const AttnP p) 
         tiles(std::integral_constant<int, 1>{}, nfull, nkt);
     }
     bf16* DQ = p.dq + (long)b * p.Lq * p.lddq + h * 64;
-    if (DW_ATTN_ROWSTORE && NW <= 7 && (p.lddq & 7) == 0 && ((uintptr_t)p.dq & 15) == 0) {
+    if ((p.lddq & 7) == 0 && ((uintptr_t)p.dq & 15) == 0) {
         __syncthreads();
         store_rows(DQ, p.lddq, qb0 + wave * 32, p.Lq, smem + wave * 4608, lane, acc[0], acc[1], p.scale);
     } else {
@@ -731,8 +519,12 @@ __global__ __launch_bounds__(64 * NW, 3) void attn_bwd_dq_kernel(const AttnP p) 
 //   S = Q.K^T, dP = dO.V^T  (rows = queries in registers, column = key = lane&31)
 //   dV^T[d][key] += dO^T . P,   dK^T[d][key] += Q^T . dS
 // ---------------------------------------------------------------------------------------------------------------
-template <bool CAUSAL, bool FS, int OCC, int NW = 4>
-__global__ __launch_bounds__(64 * NW, OCC) void attn_bwd_dkv_kernel(const AttnP p) {
+// Waves per SIMD: the non-causal kernel is compiled for 3 (168 registers; since the accumulators start from the -lse / -delta
+// tables it spills 1-2 registers instead of 14), the causal one for 2 (since the tile staging went to scalar bases it needs 172
+// registers -- at 168 it spills 9).
+template <bool CAUSAL>
+__global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const AttnP p) {
+    constexpr int NW = 4;   // waves per workgroup
     // [buf][Q tile 8K | dO tile 8K | lse 64 f32 | delta 64 f32]
     constexpr int STG = 16384 + 512;
     __shared__ __attribute__((aligned(1024))) char smem[2 * 17408];
@@ -768,8 +560,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_bwd_dkv_kernel(const AttnP 
 
     auto stage = [&](int qt, int buf, int lane) __attribute__((always_inline)) {
         char* base = smem + buf * 17408;
-        stage_tile64<NW, FS>(Q, p.ldq, qt * 64, p.Lq, base, wave, lane);
-        stage_tile64<NW, FS>(DO, p.lddo, qt * 64, p.Lq, base + 8192, wave, lane);
+        stage_tile64<NW>(Q, p.ldq, qt * 64, p.Lq, base, wave, lane);
+        stage_tile64<NW>(DO, p.lddo, qt * 64, p.Lq, base + 8192, wave, lane);
         if (wave < 2) {  // waves 0,1: 64 lse + 64 delta values through the same async path (4 B per lane; scalar base, 32-bit lane offset)
             int qi = qt * 64 + lane;
             qi = qi < p.Lq ? qi : p.Lq - 1;
@@ -802,7 +594,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_bwd_dkv_kernel(const AttnP 
         // mask needed on the query tail, on a partially valid key block, or on the causal diagonal
         const bool need_mask = MODE == 1 || (MODE == 2 && (((qt + 1) * 64 > p.Lq) || (wk0 + 31 >= p.Lk) || (CAUSAL && wk0 + 31 > qt * 64)));
         if (CAUSAL && wk0 > qt * 64 + 63) continue;  // all 64 queries of this tile precede every key of this wave
-        if (DW_ATTN_IDLE_SKIP && wk0 >= p.Lk) continue;               // none of this wave's 32 keys exists
+        if (wk0 >= p.Lk) continue;                                    // none of this wave's 32 keys exists
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             // accumulators start from -lse/scale and -delta of their query rows (register r <-> query
@@ -868,7 +660,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_bwd_dkv_kernel(const AttnP 
     }
     bf16* DK = p.dk + (long)b * p.Lk * p.lddk + h * 64;
     bf16* DV = p.dv + (long)b * p.Lk * p.lddv + h * 64;
-    if (DW_ATTN_ROWSTORE && NW <= 7 && ((p.lddk | p.lddv) & 7) == 0 && (((uintptr_t)p.dk | (uintptr_t)p.dv) & 15) == 0) {
+    if (((p.lddk | p.lddv) & 7) == 0 && (((uintptr_t)p.dk | (uintptr_t)p.dv) & 15) == 0) {
         __syncthreads();
         store_rows(DK, p.lddk, kb0 + wave * 32, p.Lk, smem + wave * 4608, lane, ak[0], ak[1], p.scale);
         store_rows(DV, p.lddv, kb0 + wave * 32, p.Lk, smem + wave * 4608, lane, av[0], av[1], 1.0f);
@@ -884,19 +676,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_bwd_dkv_kernel(const AttnP 
     }
 }
 
-// bit 0: dq kernel, bit 1: dkv kernel use the 32-bit-offset tile staging; bit 2: dkv kernel compiled for 3 waves per
-// SIMD (168 registers; since the accumulators start from the -lse/-delta tables it spills 1-2 registers instead of 14)
-int g_attn_bwd_stage = 5;  // (dw_debug_set key 3; 5 measured best: 1.65 vs 1.75 ms per encoder-layer backward)
-int g_attn_bwd_waves = 4;  // dw_debug_set key 17: 4 / 12 waves per workgroup of the non-causal backward kernels (12: 384 stationary
-                           // rows per workgroup, a third of the tile staging -- measured neutral at the encoder shape, slower at 448 x 1500)
-int g_attn_fwd_waves = 4;  // dw_debug_set key 16: 4 / 8 waves (x 32 queries) per workgroup of the non-causal forward kernel (8: half
-int g_attn_fwd_pipe = 0;      // dw_debug_set key 26: non-causal forward on attn_fwd_pipe_kernel (scores of tile t+1 under the softmax of tile t)
-                           // the K/V staging per query -- measured neutral: the kernel is not bound by the staging traffic)
 int g_attn_plain_order = 0; // dw_debug_set key 18
 int g_attn_defer = DW_ATTN_DEFER;  // dw_debug_set key 23: the forward's deferred-maximum threshold (0 = exact running maximum; the
                                    // A/B of tests/test_sharp_parity_gpu.py prices this deviation on peaked attention rows)
-int g_attn_ablate = 0;     // dw_debug_set key 15 (DW_ABLATE builds)
-int g_attn_decode = 1;     // dw_debug_set key 4: 1 = single-query attention runs the streaming decode kernel
+int g_attn_decode = 1;     // dw_debug_set key 4: 1 = single-query attention runs the streaming decode kernel, 0 = the tile kernel
 static int check_ld(int64_t ld) { return (ld & 7) ? DW_EINVAL : DW_OK; }
 
 extern "C" int dw_attn_fwd_ex(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Lq,
@@ -934,36 +717,15 @@ extern "C" int dw_attn_fwd_ex(const void* q, const void* k, const void* v, void*
         // one query per (batch, head): the streaming decode kernel.  The mask is void for a single LAST query (causal 0 and 2);
         // with causal == 1 the one query is query 0 and sees key 0 only: that combination takes the tile kernel below
         const size_t smem = (((size_t)Lk + 3) & ~(size_t)3) * 4 + 16 * 64 * 4 + 2 * 16 * 4;
-        if (Lk >= 512 && Lk <= 16 * 8 * 12 && (g_attn_decode & 2))   // (measured slower: 111 registers -> one workgroup per CU)
-            hipLaunchKernelGGL((attn_decode_kernel<16, true>), dim3(1, H, B), dim3(1024), smem, s, p);
-        else if (Lk >= 512) hipLaunchKernelGGL((attn_decode_kernel<16, false>), dim3(1, H, B), dim3(1024), smem, s, p);
-        else hipLaunchKernelGGL((attn_decode_kernel<4, false>), dim3(1, H, B), dim3(256), smem, s, p);
+        if (Lk >= 512) hipLaunchKernelGGL(attn_decode_kernel<16>, dim3(1, H, B), dim3(1024), smem, s, p);
+        else hipLaunchKernelGGL(attn_decode_kernel<4>, dim3(1, H, B), dim3(256), smem, s, p);
         DW_CHECK_LAUNCH();
         return DW_OK;
     }
-    const int g4 = (Lq + 127) / 128;
-    dim3 grid(g4 * H * B), block(256);
+    dim3 grid(((Lq + 127) / 128) * H * B), block(256);
     p.plain_order = g_attn_plain_order;
     p.defer = (float)g_attn_defer;
-#ifdef DW_ABLATE
-    if (!causal && g_attn_ablate) {
-        switch (g_attn_ablate) {
-#define ABLC(v) case v: hipLaunchKernelGGL((attn_fwd_kernel<false, 4, v>), grid, block, 0, s, p); break;
-            ABLC(1) ABLC(2) ABLC(4) ABLC(6) ABLC(8) ABLC(24) ABLC(32) ABLC(64) ABLC(7) ABLC(31) ABLC(30)
-#undef ABLC
-            default: return DW_EINVAL;
-        }
-        return DW_OK;
-    }
-#endif
-    // 256 queries per workgroup (8 waves) where that pads no more than 128 would and still fills the chip: the K/V tiles
-    // are fetched and written to LDS once per 256 queries (1500 -> 1536 and 448 -> 512 either way)
-    const int g8 = (Lq + 255) / 256;
     if (causal) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, s, p);
-    else if (g_attn_fwd_pipe == 2 && Lk > 64) hipLaunchKernelGGL((attn_fwd_pipe_kernel<4, 2>), grid, block, 0, s, p);
-    else if (g_attn_fwd_pipe && Lk > 64) hipLaunchKernelGGL((attn_fwd_pipe_kernel<4, 3>), grid, block, 0, s, p);
-    else if (g_attn_fwd_waves == 8 && g8 * 2 == g4 && (long)g8 * H * B >= 512)
-        hipLaunchKernelGGL((attn_fwd_kernel<false, 8>), dim3(g8 * H * B), dim3(512), 0, s, p);
     else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, s, p);
     DW_CHECK_LAUNCH();
     return DW_OK;
@@ -997,8 +759,8 @@ extern "C" int dw_attn_fwd_varlen(const void* q, const void* k, const void* v, v
     p.defer = (float)g_attn_defer;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(((max_q + 127) / 128) * H * n_seq), block(256);
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<true, 4, 0, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, 4, 0, true>), grid, block, 0, s, p);
+    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, 0, s, p);
     DW_CHECK_LAUNCH();
     return DW_OK;
 }
@@ -1040,30 +802,13 @@ extern "C" int dw_attn_bwd_ex(const void* q, const void* k, const void* v, const
     p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk; p.scale = scale;
     p.dq_colsum = dq_colsum; p.dv_colsum = dv_colsum;
     hipStream_t s = (hipStream_t)stream;
-    const int q4 = (Lq + 127) / 128, k4 = (Lk + 127) / 128;
-    dim3 gq(q4 * H * B), gk(k4 * H * B), block(256);
+    dim3 gq(((Lq + 127) / 128) * H * B), gk(((Lk + 127) / 128) * H * B), block(256);
     p.plain_order = g_attn_plain_order;
     p.defer = (float)g_attn_defer;
-    const int fs = g_attn_bwd_stage;
-    if (causal) {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), gq, block, 0, s, p);
-        // (two waves per SIMD: since the tile staging went to scalar bases the causal kernel needs 172 registers -- at 168 it spills 9)
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, false, 2>), gk, block, 0, s, p);
-    } else {
-        // 384 stationary rows (12 waves = the three waves per SIMD the registers allow, as ONE workgroup) where that pads
-        // no more than 128 would: the streamed tiles are fetched and written to LDS once per 384 rows (1500 -> 1536)
-        const int q12 = (Lq + 383) / 384, k12 = (Lk + 383) / 384;
-        const bool dq12 = g_attn_bwd_waves == 12 && q12 * 3 == q4 && (long)q12 * H * B >= 256;
-        const bool dkv12 = g_attn_bwd_waves == 12 && k12 * 3 == k4 && (long)k12 * H * B >= 256;
-        if (dq12) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true, 12>), dim3(q12 * H * B), dim3(768), 0, s, p);
-        else if (fs & 1) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, block, 0, s, p);
-        else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), gq, block, 0, s, p);
-        if (dkv12) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, 3, 12>), dim3(k12 * H * B), dim3(768), 0, s, p);
-        else if ((fs & 6) == 6) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, true, 3>), gk, block, 0, s, p);
-        else if (fs & 4) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, 3>), gk, block, 0, s, p);
-        else if (fs & 2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, true, 2>), gk, block, 0, s, p);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, false, 2>), gk, block, 0, s, p);
-    }
+    if (causal) hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, gq, block, 0, s, p);
+    else hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, gq, block, 0, s, p);
+    if (causal) hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, gk, block, 0, s, p);
+    else hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, gk, block, 0, s, p);
     DW_CHECK_LAUNCH();
     return DW_OK;
 }

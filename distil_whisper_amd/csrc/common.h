@@ -210,10 +210,10 @@ __device__ __forceinline__ void glds4_so(const void* sbase, unsigned voff, unsig
 __device__ __forceinline__ unsigned lds_addr_of(const void* lds) {       // wave-uniform LDS byte address of a __shared__ object
     return __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lds_void_t*)lds);
 }
-template <int NW, bool FAST = true>
+template <int NW>
 __device__ __forceinline__ void stage_tile64(const bf16* base, long row_stride, int row0, int nrows, char* lds,
                                              int wave, int lane) {
-    static_assert(NW == 4 || NW == 8 || NW == 12 || NW == 2, "chunk c = wave + i * NW: rows 8 c + (lane >> 3)");
+    static_assert(NW == 4, "chunk c = wave + i * NW: rows 8 c + (lane >> 3)");
     const int ld = (int)row_stride;
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(lds_void_t*)lds);
     if (row0 + 64 <= nrows) {

@@ -35,17 +35,11 @@ int dw_gemm_wp16_tt_launch(const GemmP& p, hipStream_t s);
 int dw_gemm_wp16_nn_small_launch(const GemmP& p, hipStream_t s);             // gemm_wp16_small.hip (the small-M rule's 256-row launches)
 int dw_gemm_wp16_nt_small_launch(const GemmP& p, hipStream_t s);
 
-extern int g_attn_bwd_stage;  // attention.hip
-extern int g_attn_decode;
-extern int g_attn_ablate;
-extern int g_attn_fwd_waves;
-extern int g_attn_fwd_pipe;
+extern int g_attn_decode;     // attention.hip
 extern int g_attn_plain_order;
 extern int g_attn_defer;
-extern int g_attn_bwd_waves;
 extern int g_logmel_mfma;     // logmel.hip
 extern int g_decode_fuse_off; // decode.hip
-extern int g_skinny_wide;     // gemm_skinny.hip
 extern int g_ln_variant;      // norm.hip
 // dw_debug_set key 0: which kernels dw_gemm_bf16 may choose (gemm_choose below).  Every kernel produces bit-identical results (same
 // fp32 chain over k per output element): tests/test_kernels_gpu.py.
@@ -83,23 +77,17 @@ int g_gemm_strip_budget = 4;   // x 512 KiB of L2 for the resident strip of B ti
 extern "C" int dw_debug_set(int key, int value) {
     if (key == 0) { if (value < GEMM_RULE || value > GEMM_FORCE_320) return DW_EINVAL; g_gemm_mode = value; return DW_OK; }
     if (key == 1) { g_gemm_strip = value; return DW_OK; }
-    if (key == 3) { g_attn_bwd_stage = value; return DW_OK; }
-    if (key == 4) { g_attn_decode = value; return DW_OK; }
+    if (key == 4) { if (value < 0 || value > 1) return DW_EINVAL; g_attn_decode = value; return DW_OK; }
     if (key == 5) { g_logmel_mfma = value; return DW_OK; }
     if (key == 6) { g_gemm_strip_budget = value; return DW_OK; }
     if (key == 7) { g_decode_fuse_off = value; return DW_OK; }
-    if (key == 8) { g_skinny_wide = value; return DW_OK; }
     if (key == 10) { g_gemm_dynamic = value; return DW_OK; }
     if (key == 11) { g_gemm_stage_next = value; return DW_OK; }
-    if (key == 17) { g_attn_bwd_waves = value; return DW_OK; }
     if (key == 21) { g_ln_variant = value; return DW_OK; }
     if (key == 22) { g_gemm_row_tail = value; return DW_OK; }
     if (key == 25) { if (value < 0 || value > 1) return DW_EINVAL; g_gemm_small_m = value; return DW_OK; }
-    if (key == 26) { g_attn_fwd_pipe = value; return DW_OK; }
     if (key == 18) { g_attn_plain_order = value; return DW_OK; }
     if (key == 23) { if (value < 0 || value > 64) return DW_EINVAL; g_attn_defer = value; return DW_OK; }
-    if (key == 16) { g_attn_fwd_waves = value; return DW_OK; }
-    if (key == 15) { g_attn_ablate = value; return DW_OK; }
     if (key == 9) { if (value < 8 || value > 256 || (value & 7)) return DW_EINVAL; g_gemm_cus = value; return DW_OK; }
     return DW_EINVAL;
 }

@@ -27,7 +27,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 constexpr int SK_MAXS = 10;   // 32-deep k steps a wave keeps in registers (10 x 16 B of W + as much of A per lane)
 constexpr int SK_MAXW = 16;   // waves per workgroup
-int g_skinny_wide = 5;        // dw_debug_set key 8: bit 0 wide (64 columns per workgroup) variant for the LM head; bit 1: LayerNorm variants keep ONE column block per workgroup; bits 2-3: columns per workgroup of the projections back to d_model (4: 8 columns, the default; 0: 4; 12: 16)
 
 // 8 consecutive elements of the LayerNorm input (f32 or bf16) as floats
 template <bool XBF>
@@ -50,15 +49,15 @@ __device__ __forceinline__ void ld_x8(const void* x, long off, float (&v)[8]) {
 // 256 CUs (18.2 us against 10.5 for the 240 blocks of the QKV projection, profiles/r6_decode_step_sequence.md) and every
 // workgroup repeated the row statistics of all 16 rows for 40 KB of weights.  With two blocks per workgroup the launch is 160 /
 // 120 workgroups -- one round -- and the LayerNorm work per weight byte halves.
-// VR (plain variant only): weight rows (output columns) a workgroup owns, 16 / 8 / 4.  A projection back to d_model has N / 16 = 80
+// VR (plain variant only): weight rows (output columns) a workgroup owns, 16 / 8.  A projection back to d_model has N / 16 = 80
 // workgroups at D = 1280 -- 80 of the 256 CUs pull the weights, and a CU sustains ~25 GB/s of misses (fc2's 13 MB: 12 us against a
-// 5.5 us launch floor).  With 8 or 4 valid rows per workgroup (the other lanes of the 16-row MFMA operand stay zero: the matrix
-// pipe is idle here anyway) the same bytes are pulled by 160 / 320 workgroups.
+// 5.5 us launch floor).  With 8 valid rows per workgroup (the other lanes of the 16-row MFMA operand stay zero: the matrix
+// pipe is idle here anyway) the same bytes are pulled by 160 workgroups.
 template <int MB, int LN, int NB = 1, int VR = 16>
 __global__ __launch_bounds__(LN ? 256 : 64 * SK_MAXW) void gemm_skinny_kernel(const GemmP p, int nw, int steps_total) {
     extern __shared__ float red[];  // [nw][NB][MB][64][4]
     static_assert(NB == 1 || LN != 0, "several column blocks per workgroup: the LayerNorm variants");
-    static_assert(VR == 16 || (LN == 0 && NB == 1 && (VR == 8 || VR == 4)), "partial column blocks: the plain variant");
+    static_assert(VR == 16 || (LN == 0 && NB == 1 && VR == 8), "partial column blocks: the plain variant");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n0 = blockIdx.x * (VR == 16 ? 16 * NB : VR);
@@ -330,7 +329,7 @@ int dw_gemm_skinny_launch(const GemmP& p, hipStream_t s) {
     if (nw > SK_MAXW) nw = SK_MAXW;
     if ((steps + nw - 1) / nw > SK_MAXS) return DW_EINVAL;
     const int mb = (p.m + 15) / 16;
-    if ((g_skinny_wide & 1) && !p.bias && !p.act && !p.r && !p.ln_x && !p.kv_out && nw <= 4 && p.n >= 16384 && mb <= 2) {
+    if (!p.bias && !p.act && !p.r && !p.ln_x && !p.kv_out && nw <= 4 && p.n >= 16384 && mb <= 2) {
         constexpr int NB = 4;
         dim3 grid((p.n + 16 * NB - 1) / (16 * NB)), block(64 * nw);
         const size_t lds = (size_t)nw * NB * mb * 64 * 4 * sizeof(float);
@@ -344,10 +343,10 @@ int dw_gemm_skinny_launch(const GemmP& p, hipStream_t s) {
     if (p.ln_x) {
         const bool xbf = p.ln_x_dtype == DW_BF16;
         // two column blocks per workgroup when that is what brings the launch into one round of the CUs (or halves a round that
-        // fits already, one row block only: the LayerNorm prologue is the same work per workgroup); dw_debug_set key 8 bit 1 = off
+        // fits already, one row block only: the LayerNorm prologue is the same work per workgroup)
         // (measured at batch 16, D = 1280: fc1's 320 blocks 18.2 -> 12.5 us; the QKV projection's 240 blocks fit one round already
         // and LOSE 1.5 us as 120 workgroups -- fewer CUs pulling the weights)
-        if (mb == 1 && (g_skinny_wide & 2) == 0 && p.n % 32 == 0 && p.n / 16 > 256) {
+        if (mb == 1 && p.n % 32 == 0 && p.n / 16 > 256) {
             dim3 grid2(p.n / 32);
             if (!xbf) hipLaunchKernelGGL((gemm_skinny_kernel<1, 1, 2>), grid2, block, 2 * lds, s, p, nw, steps);
             else hipLaunchKernelGGL((gemm_skinny_kernel<1, 2, 2>), grid2, block, 2 * lds, s, p, nw, steps);
@@ -358,14 +357,12 @@ int dw_gemm_skinny_launch(const GemmP& p, hipStream_t s) {
         else if (mb == 1) hipLaunchKernelGGL((gemm_skinny_kernel<1, 2>), grid, block, lds, s, p, nw, steps);
         else if (!xbf) hipLaunchKernelGGL((gemm_skinny_kernel<2, 1>), grid, block, lds, s, p, nw, steps);
         else hipLaunchKernelGGL((gemm_skinny_kernel<2, 2>), grid, block, lds, s, p, nw, steps);
-    } else if (mb == 1 && p.n / 16 <= 128 && (g_skinny_wide & 12) != 12) {
+    } else if (mb == 1 && p.n / 16 <= 128) {
         // few column blocks (a projection back to d_model): 8 columns per workgroup so that 160 instead of 80 CUs pull the weights.
         // Measured at batch 16, D = 1280 (eager token step, tools/decode_profile.py): 16 columns 0.2195 ms, 8 columns 0.2161, 4 columns
         // 0.2319 -- every workgroup fetches the activation slice of all 16 rows, so more workgroups multiply the L2 traffic
         // (fc2: 160 KB per workgroup) and four columns lose what the spread wins.
-        // (dw_debug_set key 8 bits 2-3: 0 -> 4 columns, 4 -> 8 columns, 12 -> 16 columns as before)
-        if (g_skinny_wide & 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 0, 1, 8>), dim3(p.n / 8), block, lds, s, p, nw, steps);
-        else hipLaunchKernelGGL((gemm_skinny_kernel<1, 0, 1, 4>), dim3(p.n / 4), block, lds, s, p, nw, steps);
+        hipLaunchKernelGGL((gemm_skinny_kernel<1, 0, 1, 8>), dim3(p.n / 8), block, lds, s, p, nw, steps);
     } else if (mb == 1) hipLaunchKernelGGL((gemm_skinny_kernel<1, 0>), grid, block, lds, s, p, nw, steps);
     else if (mb == 2) hipLaunchKernelGGL((gemm_skinny_kernel<2, 0>), grid, block, lds, s, p, nw, steps);
     else hipLaunchKernelGGL((gemm_skinny_kernel<4, 0>), grid, block, lds, s, p, nw, steps);

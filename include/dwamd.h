@@ -547,12 +547,12 @@ int dw_selftest_tr16(int32_t* out, void* stream);
  *   key 10  dynamic per-XCD tile hand-out (default 1);   key 11  GEMM staging: bit 7 (128) requests the next tile's first
  *           operand tile before the epilogue at any K (the rule does so for K <= 1024); bit 4 (16) makes the 16x16x32
  *           kernels skip their epilogue (profiling: nothing is stored); other bits unused (default 1)
- *   key 3   attention backward variant (bit 0 dQ, bit 1 dK/dV fast tile staging, bit 2 dK/dV at 3 waves per SIMD -- bits 1
- *           and 2 apply to the NON-causal dK/dV kernel only: the causal launch always runs two waves per SIMD; default 5);   key 4  single-query attention kernel (bit 0 on [default], bit 1 all-loads-up-front variant)
+ *   key 4   single-query attention (Lq == 1): 1 = the streaming decode kernel (default), 0 = the tile kernel; other values
+ *           are DW_EINVAL
  *   key 5   log-mel DFT on the matrix cores (default 1);   key 7  decode-step fusions off (bit 0 LayerNorm-on-load,
  *           bit 1 K/V append, bit 2 self-attention with its q / k / v projection inside, bit 3 cross-attention with its q
- *           projection inside; default 4);   key 8  token-step GEMVs, bit mask (default 5): bit 0 wide LM-head kernel; bit 1 LayerNorm-on-load kernels keep one
- *           column block per workgroup; bits 2-3 columns per workgroup of the projections back to d_model (4: 8, 0: 4, 12: 16)
+ *           projection inside; default 4)
+ *   key 18  attention tile kernels take (tile, head, batch) in plain launch order instead of the XCD-aware order (default 0)
  *   key 21  LayerNorm kernels: bit 0 persistent fp32-input forward with next-row prefetch (bits 8-11: workgroups per CU),
  *           bit 1 backward with next-row / residual-gradient prefetch at two waves per SIMD (default 3; tools/ln_ab.py)
  *   key 22  wide row-major 256-row launches hand a partial last row block (<= 128 rows) to the 128-tile kernel when the full
@@ -563,9 +563,7 @@ int dw_selftest_tr16(int32_t* out, void* stream);
  *   key 25  outputs with fewer than two rounds of 256-row tiles (the decoders' M = 32 x live positions): kernel chosen by the
  *           rounds of the CUs it needs among 128 x 256 tiles in a three-stage operand ring (csrc/gemm_wp8_m128.hip), 256 x 256
  *           on 16x16x32 and 320 x 256 (default 1; 0 = the lock-step 128 x 128 kernel; bit-identical)
- *   key 26  non-causal attention forward on the software-pipelined kernel (scores of key tile t+1 under the softmax of tile
- *           t, three K / V stages; 1: three waves per SIMD, 2: two).  Default 0: measured 8 % / 15 % SLOWER than the four-waves-
- *           per-SIMD kernel at the encoder shape (tools/attn_pipe_ab.py), bit-identical -- kept as the A/B of that design
+ * Every other key is DW_EINVAL (keys 3, 8, 15, 16, 17 and 26 selected experiment kernels that are retired: DESIGN_HISTORY.md).
  */
 int dw_debug_set(int key, int value);
 

@@ -14,8 +14,9 @@ tests/test_attention_edges.py).
   restatement's worst row in every case).  F = the smallest of 2, 3, 4 that is at least 1.5 x the ratio: o 2, dq 3, dk 3, dv 2.
   lse against float64: at most 8.6e-7 at unit scale, 5.4e-6 with q and k scaled by 4 (lse of several tens there: 1.4 fp32 ulps); bound 4 x that,
   rounded up to one digit = 3e-5 (the suite's bound elsewhere is 2e-3).
-* The store_t fallback (output pitch not a multiple of 8 elements, or a base that is 8- but not 16-byte aligned), the library
-  variants behind dw_debug_set keys 3, 4, 16, 17, 18 and 26 (same bits as the default dispatch) and the argument checks."""
+* The store_t fallback (output pitch not a multiple of 8 elements, or a base that is 8- but not 16-byte aligned), the plain
+  workgroup order behind dw_debug_set key 18 (same bits as the default dispatch) and the argument checks, those of dw_debug_set
+  included (the keys of retired experiment kernels are DW_EINVAL)."""
 import contextlib
 
 import pytest
@@ -29,7 +30,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F_BOUND = {"o": 2.0, "dq": 3.0, "dk": 3.0, "dv": 2.0}      # see the module docstring
 LSE_BOUND = 3e-5
-DEBUG_DEFAULT = {3: 5, 4: 1, 16: 4, 17: 4, 18: 0, 26: 0}   # csrc/attention.hip
+DEBUG_DEFAULT = {4: 1, 18: 0}   # csrc/attention.hip
 
 
 @pytest.fixture(scope="module")
@@ -120,13 +121,9 @@ def test_census_bottom_right_against_padded_cache(ops, B, Lq, Lk, pitch):
 
 @pytest.mark.parametrize("causal", [0, 2])
 def test_census_single_query(ops, causal):
-    """The streaming kernel over its switch to 16 waves at 512 keys, the all-loads-up-front variant (key 4 = 3, 512 ... 1536 keys) and
-    the hand-over to the tile kernel above 8192."""
+    """The streaming kernel over its switch to 16 waves at 512 keys and the hand-over to the tile kernel above 8192."""
     for Lk in ar.ONE_LK:
         census(ops, 1, 1, Lk, causal)
-        if 512 <= Lk <= 1536:
-            with debug(ops, 4, 3):
-                census(ops, 1, 1, Lk, causal, name="key 4 = 3: ")
     for Lk in ar.ONE_LK_LSE_ONLY:
         census(ops, 1, 1, Lk, causal, counts=False)
 
@@ -263,7 +260,7 @@ def test_fallback_stores_bottom_right_forward(ops, pad, off):
     assert torch.equal(o, o0) and torch.equal(lse, lse0)
 
 
-# ---- 6. library variants: same bits as the default dispatch ----------------------------------------------------------------------
+# ---- 6. library variant: same bits as the default dispatch -----------------------------------------------------------------------
 def _fwd_all(ops, inp, B, H, Lq, Lk, causal=0):
     q, k, v, _ = inp
     return ops.attn_fwd(q, k, v, B, H, Lq, Lk, causal, ar.SCALE)
@@ -280,62 +277,6 @@ def _same_bwd(got, want):
     assert all(torch.equal(a, b) for a, b in zip(got[:3], want[:3]))
     # (the column sums are float atomics over the same addends: equal up to their order)
     assert relerr(got[3], want[3]) <= 1e-5 and relerr(got[4], want[4]) <= 1e-5
-
-
-@pytest.mark.parametrize("B,H,Lq,Lk", [(2, 2, 100, 65), (1, 1, 129, 130), (1, 2, 33, 447)])
-def test_variant_pipelined_forward_same_bits(ops, B, H, Lq, Lk):
-    """Key 26 (1: three workgroups per CU, 2: two): selected above 64 keys -- 65 is the first length that runs it."""
-    inp = ar.sweep_inputs(B, H, Lq, Lk, device=DEV)
-    o0, lse0 = _fwd_all(ops, inp, B, H, Lq, Lk)
-    for value in (1, 2):
-        with debug(ops, 26, value):
-            o, lse = _fwd_all(ops, inp, B, H, Lq, Lk)
-        assert torch.equal(o, o0) and torch.equal(lse, lse0), value
-
-
-@pytest.mark.parametrize("B,H,Lq,Lk", [(64, 8, 200, 100), (64, 8, 256, 64)])
-def test_variant_8_wave_forward_same_bits(ops, B, H, Lq, Lk):
-    """Key 16 = 8: 256 queries per workgroup, taken where 256-row tiles pad no more than 128-row ones and 512 workgroups remain;
-    200 rows leave idle waves."""
-    assert (Lq + 255) // 256 * 2 == (Lq + 127) // 128 and (Lq + 255) // 256 * H * B >= 512
-    inp = ar.sweep_inputs(B, H, Lq, Lk, device=DEV)
-    o0, lse0 = _fwd_all(ops, inp, B, H, Lq, Lk)
-    with debug(ops, 16, 8):
-        o, lse = _fwd_all(ops, inp, B, H, Lq, Lk)
-    assert torch.equal(o, o0) and torch.equal(lse, lse0)
-
-
-@pytest.mark.parametrize("B,H,Lq,Lk", [(64, 4, 300, 300), (64, 4, 130, 384)])
-def test_variant_12_wave_backward_same_bits(ops, B, H, Lq, Lk):
-    """Key 17 = 12: 384 stationary rows per workgroup.  300 x 300 takes both 12-wave kernels, 130 x 384 the dK/dV one only."""
-    inp = ar.sweep_inputs(B, H, Lq, Lk, device=DEV)
-    o0, lse0 = _fwd_all(ops, inp, B, H, Lq, Lk)
-    want = _bwd_all(ops, inp, o0, lse0, B, H, Lq, Lk)
-    with debug(ops, 17, 12):
-        got = _bwd_all(ops, inp, o0, lse0, B, H, Lq, Lk)
-    _same_bwd(got, want)
-
-
-def test_variant_backward_staging_same_bits(ops):
-    """Key 3 (default 5): bit 0 / 1 the 32-bit-offset tile staging of the dQ / dK/dV kernel, bit 2 the dK/dV kernel at three waves per SIMD."""
-    B, H, Lq, Lk = 2, 2, 100, 130
-    inp = ar.sweep_inputs(B, H, Lq, Lk, device=DEV)
-    o0, lse0 = _fwd_all(ops, inp, B, H, Lq, Lk)
-    want = _bwd_all(ops, inp, o0, lse0, B, H, Lq, Lk)
-    for value in range(8):
-        with debug(ops, 3, value):
-            got = _bwd_all(ops, inp, o0, lse0, B, H, Lq, Lk)
-        _same_bwd(got, want)
-
-
-@pytest.mark.parametrize("Lk", [512, 1500, 1536])
-def test_variant_single_query_loads_up_front_same_bits(ops, Lk):
-    B, H = 3, 2
-    inp = ar.sweep_inputs(B, H, 1, Lk, device=DEV)
-    o0, lse0 = _fwd_all(ops, inp, B, H, 1, Lk)
-    with debug(ops, 4, 3):
-        o, lse = _fwd_all(ops, inp, B, H, 1, Lk)
-    assert torch.equal(o, o0) and torch.equal(lse, lse0)
 
 
 def test_variant_plain_workgroup_order_same_bits(ops):
@@ -394,3 +335,23 @@ def test_invalid_arguments_are_rejected_and_write_nothing(ops):
     b()
     torch.cuda.synchronize()
     assert not o.untouched() and not dq.untouched()
+
+
+RETIRED_KEYS = (3, 8, 15, 16, 17, 26)       # experiment kernels that left the library (DESIGN_HISTORY.md)
+
+
+def test_debug_set_rejects_retired_keys_and_values(ops):
+    """A retired key answers DW_EINVAL like any unknown key, for its old default and for the value that selected the experiment;
+    key 4 keeps 0 (tile kernel) and 1 (streaming kernel) only."""
+    for key in RETIRED_KEYS:
+        for value in (0, 1, 2, 4, 5, 8, 12):
+            assert ops.lib.dw_debug_set(key, value) == -1, (key, value)
+    try:
+        for value in (2, 3, -1):
+            assert ops.lib.dw_debug_set(4, value) == -1, value
+        for value in (0, 1):
+            assert ops.lib.dw_debug_set(4, value) == 0, value
+    finally:
+        ops.lib.dw_debug_set(4, DEBUG_DEFAULT[4])
+    # a rejected value left the switch alone: a single query still runs (either kernel gives the census counts)
+    census(ops, 1, 1, 600, 0)

@@ -36,7 +36,7 @@ for i, path in [(1, base)] + [(j, base.replace("_base.so", f"_base{j}.so")) for 
     if os.path.exists(path): libs[i] = _oh.load_library(path)
 allkeys = sorted({k for c in configs for k in c if isinstance(k, int)})
 from distil_whisper_amd.engine import WhisperEngine
-DEF = {0: 0, 1: 0, 3: 5, 6: 4, 9: 256, 10: 1, 11: 1, 22: 1, 23: 8, 25: 1, 26: 0, 27: 0, 28: 0}
+DEF = {0: 0, 1: 0, 6: 4, 9: 256, 10: 1, 11: 1, 22: 1, 23: 8, 25: 1}
 step(); torch.cuda.synchronize()
 res = [[] for _ in configs]
 NS = int(os.environ.get("DW_NS", "3"))

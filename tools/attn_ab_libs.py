@@ -8,20 +8,16 @@ ops = HipOps("cuda:0")
 _new = ops.lib
 _bp = os.path.join(os.path.dirname(ops_hip.LIB_PATH), "libdwamd_base.so")
 _base = ops_hip.load_library(_bp) if os.path.exists(_bp) else _new
-# tag -> (library, {dw_debug_set key: value}): 16 / 17 = waves per workgroup of the forward / backward kernels, 18 = 1: plain
-# workgroup order instead of the XCD-aware one
-libs = {"base": (_base, {16: 4, 17: 4, 18: 0}), "new": (_new, {16: 4, 17: 4, 18: 0})}
+# tag -> (library, {dw_debug_set key: value}): 18 = 1: plain workgroup order instead of the XCD-aware one
+libs = {"base": (_base, {18: 0}), "new": (_new, {18: 0})}
 if os.environ.get("DW_ATTN_ALL_LIBS"):   # every libdwamd_base[N].so next to the library (compiler-flag variants, tools/build_variant_lib.sh); "base" = the current build
-    libs = {"base": (_new, {16: 4, 17: 4, 18: 0})}
+    libs = {"base": (_new, {18: 0})}
     for j in ("", "2", "3", "4", "5"):
         pj = _bp.replace("_base.so", f"_base{j}.so")
         if os.path.exists(pj):
-            libs[f"lib{j or 1}"] = (ops_hip.load_library(pj), {16: 4, 17: 4, 18: 0})
-if os.environ.get("DW_ATTN_STAGE"):      # dw_debug_set key 3 (bit 0: dq, bit 1: dkv 32-bit staging flag, bit 2: dkv at three waves per SIMD)
-    libs = {f"stage {v}": (_new, {16: 4, 17: 4, 18: 0, 3: v}) for v in (5, 1, 7, 3)}
-    libs["base"] = libs.pop("stage 5")
+            libs[f"lib{j or 1}"] = (ops_hip.load_library(pj), {18: 0})
 if os.environ.get("DW_ATTN_VARIANTS"):
-    libs.update({"new plain order": (_new, {16: 4, 17: 4, 18: 1}), "new 8 / 12 waves": (_new, {16: 8, 17: 12, 18: 0})})
+    libs["new plain order"] = (_new, {18: 1})
 D, H = 1280, 20
 def timed(fn, n=10):
     for _ in range(2): fn()

@@ -1,11 +1,11 @@
-"""Same-process A/B of attention kernel variants selected by dw_debug_set keys (3: backward staging / PIPE, 22: forward
-variant) at the step's shapes; results compared with the default kernels'."""
+"""Same-process A/B of the attention kernels' dw_debug_set keys (18: plain workgroup order, 23: deferred-maximum threshold of the
+forward softmax) at the step's shapes; results compared with the default's."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distil_whisper_amd.ops_hip import HipOps
 ops = HipOps("cuda:0")
 D, H = 1280, 20
-VARIANTS = {"default": {3: 5, 22: 0}}
+VARIANTS = {"default": {18: 0, 23: 8}}
 for spec in sys.argv[1:]:             # name=key:value,key:value
     name, kv = spec.split("=")
     VARIANTS[name] = dict(VARIANTS["default"])

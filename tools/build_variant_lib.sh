@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build distil_whisper_amd/libdwamd_base.so from the WORKING TREE's csrc with extra compiler flags, for same-process A/B
 # runs of a compile-time switch (tools/ab_keys.py `lib`, tools/ab_libs_gemm.py):
-#     tools/build_variant_lib.sh "-DDW_ABLATE" [output name, default libdwamd_base.so; libdwamd_base2.so = library 2 of the tools]
+#     tools/build_variant_lib.sh "-DDW_ATTN_DEFER=0" [output name, default libdwamd_base.so; libdwamd_base2.so = library 2 of the tools]
 # The file is git-ignored.
 set -e
 FLAGS="$1"
