@@ -38,9 +38,20 @@ __device__ __forceinline__ float bits2f(unsigned short u) {
 // ---- exact (erf) GELU, as transformers' GELUActivation / F.gelu(approximate='none') ------------------------
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float x) {
-    const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
-    const float pdf = 0.39894228040143268f * __expf(-0.5f * x * x);
-    return cdf + x * pdf;
+    if (x >= -4.0f) {      // (below: 3e-5 of a Gaussian's values, so that hardly a wave takes the second path)
+        const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
+        const float pdf = 0.39894228040143268f * __expf(-0.5f * x * x);
+        return cdf + x * pdf;
+    }
+    // Lower tail: 1 + erf(x / sqrt2) is a multiple of 2^-24, which is 3 % of a bf16 ulp of the result at x = -4 and all of the cdf
+    // from x = -5, and exp(-x^2 / 2) leaves the normal range at x = -13.2 while gelu' (-4e-38 there) has not.  With
+    // erfc(u) = exp(-u^2) erfcx(u), u = -x / sqrt2: gelu'(x) = exp(-x^2 / 2) * (erfcx(u) / 2 + x / sqrt(2 pi)), the exponential
+    // scaled by 2^64 where it would be subnormal.
+    const float xx = x * x * -0.72134752044448170f;                  // -x^2 / 2 * log2(e)
+    const bool far = xx < -96.0f;
+    const float e = exp2f(far ? xx + 64.0f : xx);
+    const float r = e * (0.5f * erfcxf(x * -0.70710678118654752f) + x * 0.39894228040143268f);
+    return far ? r * 0x1p-64f : r;
 }
 
 // Fast exact-erf GELU for the GEMM epilogues (Abramowitz & Stegun 7.1.26, |erf error| <= 1.5e-7: far below the
@@ -70,6 +81,11 @@ __device__ __forceinline__ void gelu_parts2(f32x2 x, f32x2& cdf, f32x2& pdf) {
 // s = 1 - tail = erf(|x| / sqrt2),  gelu(x) = x * cdf(x) = (x + |x| * s) / 2 for either sign of x -- no compare / select pair per
 // element and no separate multiply by x; cdf itself (gelu' = cdf + x * pdf, the student's stored by-product) is
 // 1/2 + copysign(s, x) / 2: one bit-field insert per element.
+// Domain: x < 2^127.  From there (the 128 largest finite bf16 values) |x| * s + x overflows before it is halved and gelu comes out
+// +inf (gelu' does not: it never forms the sum).  Halving the addends instead costs the packed instruction count nothing but moved the
+// register allocation of every GEMM kernel that inlines this epilogue, and the step measured 0.5 % slower (338.9 against 337.1 ms,
+// twice); an activation of 1.7e38 is a diverged run either way.  tests/test_frontend_edges_gpu.py sweeps every bf16 value and pins
+// the +inf there.
 __device__ __forceinline__ void gelu_y_s_pdf2(f32x2 x, f32x2& y, f32x2& s, f32x2& pdf) {
     f32x2 ax; ax[0] = fabsf(x[0]); ax[1] = fabsf(x[1]);
     const f32x2 u = ax * 0.70710678118654752f;

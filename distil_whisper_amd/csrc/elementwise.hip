@@ -309,6 +309,9 @@ extern "C" int dw_embed_fwd(const int64_t* ids, const void* tok, const void* pos
                             int out_dtype, int B, int T, int D, void* stream) {
     DW_CLEAR_ERR();
     if (!ids || !tok || !pos || !out || B <= 0 || T <= 0 || D <= 0 || (D & 3)) return DW_EINVAL;
+    // one bf16x4 (8 bytes) or f32x4 (16 bytes) per lane on the tables and on the output
+    const uintptr_t tab_mask = tab_dtype == DW_BF16 ? 7 : 15, out_mask = out_dtype == DW_BF16 ? 7 : 15;
+    if (((uintptr_t)tok & tab_mask) || ((uintptr_t)pos & tab_mask) || ((uintptr_t)out & out_mask)) return DW_EINVAL;
     const long nvec = (long)B * T * (D >> 2);
     dim3 grid((nvec + 255) / 256), block(256);
     hipStream_t s = (hipStream_t)stream;
@@ -346,6 +349,7 @@ extern "C" int dw_im2col_mel(const float* mel, void* xcol, int B, int C, int T, 
 extern "C" int dw_im2col_s2(const void* a, void* xcol, int B, int T, int C, void* stream) {
     DW_CLEAR_ERR();
     if (!a || !xcol || B <= 0 || T <= 0 || (T & 1) || C <= 0 || (C & 7)) return DW_EINVAL;
+    if (((uintptr_t)a & 15) || ((uintptr_t)xcol & 15)) return DW_EINVAL;      // bf16x8 per lane
     const long nvec = (long)B * (T / 2) * ((3 * C) >> 3);
     hipLaunchKernelGGL(im2col_s2_kernel, dim3((nvec + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16*)a,
                        (bf16*)xcol, T, C, nvec);
@@ -356,6 +360,7 @@ extern "C" int dw_im2col_s2(const void* a, void* xcol, int B, int T, int C, void
 extern "C" int dw_col2im_s2_gelu_bwd(const void* dxcol, const void* z, void* dz, int B, int T, int C, void* stream) {
     DW_CLEAR_ERR();
     if (!dxcol || !z || !dz || B <= 0 || T <= 0 || (T & 1) || C <= 0 || (C & 7)) return DW_EINVAL;
+    if (((uintptr_t)dxcol & 15) || ((uintptr_t)z & 15) || ((uintptr_t)dz & 15)) return DW_EINVAL;      // bf16x8 per lane
     const long nvec = (long)B * T * (C >> 3);
     hipLaunchKernelGGL(col2im_s2_gelu_bwd_kernel, dim3((nvec + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const bf16*)dxcol, (const bf16*)z, (bf16*)dz, T, C, nvec);
@@ -366,6 +371,8 @@ extern "C" int dw_col2im_s2_gelu_bwd(const void* dxcol, const void* z, void* dz,
 extern "C" int dw_gelu_bwd(const void* dy, int dy_dtype, const void* z, void* dz, int64_t n, void* stream) {
     DW_CLEAR_ERR();
     if (!dy || !z || !dz || n <= 0 || (n & 3)) return DW_EINVAL;
+    // bf16x4 (8 bytes) per lane on z, dz and a bf16 dy; f32x4 (16 bytes) on an fp32 dy
+    if (((uintptr_t)dy & (dy_dtype == DW_BF16 ? 7 : 15)) || ((uintptr_t)z & 7) || ((uintptr_t)dz & 7)) return DW_EINVAL;
     dim3 grid((n / 4 + 255) / 256), block(256);
     if (dy_dtype == DW_BF16)
         hipLaunchKernelGGL(gelu_bwd_kernel<true>, grid, block, 0, (hipStream_t)stream, dy, (const bf16*)z, (bf16*)dz,

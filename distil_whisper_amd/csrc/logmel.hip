@@ -22,6 +22,10 @@ __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
     else atomicMin((unsigned int*)addr, __float_as_uint(v));
 }
 
+// log10(max(v, 1e-10)): exactly -10 at the floor (log10f of the float nearest to 1e-10 is one ulp above it, which left the features
+// of a silent clip at -1.49999976 instead of (-10 + 4) / 4)
+__device__ __forceinline__ float log10_floored(float v) { return v > 1e-10f ? log10f(v) : -10.0f; }
+
 __global__ void logmel_init_kernel(float* clipmax, int batch) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < batch) clipmax[i] = -INFINITY;
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* audio, int n_s
             }
 #pragma unroll
             for (int f = 0; f < LM_FR; ++f) {
-                lm[f] = log10f(fmaxf(lm[f], 1e-10f));
+                lm[f] = log10_floored(lm[f]);
                 if (t0 + f < n_frames) bmax = fmaxf(bmax, lm[f]);
             }
         }
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(1024) void logmel_mfma_kernel(const float* audio, i
             const int m = i >> 5, f = i & 31;
             float v = 0.f;
             for (int k = s_rng[2 * m]; k < s_rng[2 * m + 1]; ++k) v = fmaf(mel_filters[k * n_mels + m], s_p[f * LM_PWLD + k], v);
-            v = log10f(fmaxf(v, 1e-10f));
+            v = log10_floored(v);
             if (t0 + f < n_frames) bmax = fmaxf(bmax, v);
             s_o[m * 33 + f] = v;
         }
@@ -278,6 +282,7 @@ extern "C" int dw_logmel(const float* audio, int batch, int n_samples, const flo
     if (batch <= 0 || n_samples < 400 || (n_samples % 160) || n_mels <= 0 || n_mels > 256) return DW_EINVAL;
     const int n_frames = n_samples / 160;
     if (((long)n_mels * n_frames) & 3) return DW_EINVAL;
+    if ((uintptr_t)out & 15) return DW_EINVAL;            // logmel_norm_kernel: f32x4 per lane
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(logmel_init_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, clipmax, batch);
     if (g_logmel_mfma) {

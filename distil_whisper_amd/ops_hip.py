@@ -257,12 +257,14 @@ class HipOps:
         self._chk(self.lib.dw_selftest_tr16(_p(out), self._stream()), "selftest_tr16")
         return out
 
-    def logmel(self, audio, filters):
+    def logmel(self, audio, filters, out=None):
         assert audio.dtype == torch.float32 and audio.dim() == 2 and audio.is_contiguous()
         assert filters.dtype == torch.float32 and filters.shape[0] == 201 and filters.is_contiguous()
         B, N = audio.shape
         M = filters.shape[1]
-        out = self.empty((B, M, N // 160), torch.float32)
+        if out is None:
+            out = self.empty((B, M, N // 160), torch.float32)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, M, N // 160)
         clip = self.empty((B,), torch.float32)
         self._chk(self.lib.dw_logmel(_p(audio), B, N, _p(filters), M, _p(self._twiddle), _p(self._window), _p(out),
                                      _p(clip), self._stream()), "logmel")
@@ -536,18 +538,18 @@ class HipOps:
                                            self._stream()), "distill_loss")
         return (losses, row_ce, row_kl) if return_rows else losses
 
-    def embed_fwd(self, ids, tok, pos, out_dtype, rows_alloc=0):
+    def embed_fwd(self, ids, tok, pos, out_dtype, rows_alloc=0, out=None):
         """rows_alloc > B*T: the output buffer gets that many rows (the extra rows are zero; callers whose GEMMs run
-        over a padded row count)."""
+        over a padded row count).  out: a contiguous [max(rows_alloc, B*T), D] buffer of out_dtype to fill instead of a new one."""
         B, T = ids.shape
         D = tok.shape[1]
         assert ids.dtype == torch.int64 and ids.is_contiguous() and tok.is_contiguous() and pos.is_contiguous()
         assert tok.dtype == pos.dtype
+        if out is None:
+            out = self.empty((max(rows_alloc, B * T), D), out_dtype)
+        assert out.dtype == out_dtype and out.is_contiguous() and out.shape == (max(rows_alloc, B * T), D)
         if rows_alloc > B * T:
-            out = self.empty((rows_alloc, D), out_dtype)
             out[B * T:].zero_()
-        else:
-            out = self.empty((B * T, D), out_dtype)
         self._chk(self.lib.dw_embed_fwd(_p(ids), _p(tok), _p(pos), _dt(tok), _p(out), _dt(out), B, T, D,
                                         self._stream()), "embed_fwd")
         return out
@@ -644,9 +646,10 @@ class HipOps:
                                         out.stride(0) * out.element_size(), _p(idx), n, rb, 1, self._stream()), "move_rows")
         return out
 
-    def add(self, a, b, out_dtype):
+    def add(self, a, b, out_dtype, out=None):
         assert a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
-        y = self.empty(a.shape, out_dtype)
+        y = self.empty(a.shape, out_dtype) if out is None else out
+        assert y.dtype == out_dtype and y.is_contiguous() and y.shape == a.shape
         self._chk(self.lib.dw_add(_p(a), _dt(a), _p(b), _dt(b), _p(y), _dt(y), a.numel(), self._stream()), "add")
         return y
 

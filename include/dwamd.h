@@ -37,7 +37,9 @@ int dw_version(void);
  * audio [batch][n_samples] f32 (n_samples = 480000), hann window 400 (periodic), hop 160, reflect-pad centre STFT,
  * power spectrum, mel_filters [201][n_mels] f32 (HF layout), log10(clamp 1e-10), max(x, clipmax-8), (x+4)/4.
  * out [batch][n_mels][n_frames] f32 with n_frames = n_samples/160.  twiddle [400][2] f32 = (cos, sin)(2*pi*i/400),
- * window [400] f32; clipmax [batch] f32 scratch (overwritten). */
+ * window [400] f32; clipmax [batch] f32 scratch (overwritten).
+ * n_samples >= 400 and a multiple of 160, 1 <= n_mels <= 256, n_mels * n_frames a multiple of 4 and `out` 16-byte aligned (the
+ * normalisation pass moves four floats per lane); DW_EINVAL otherwise, before any launch. */
 int dw_logmel(const float* audio, int batch, int n_samples, const float* mel_filters, int n_mels,
               const float* twiddle, const float* window, float* out, float* clipmax, void* stream);
 
@@ -192,7 +194,9 @@ int dw_distill_loss_w(const void* s_logits, const void* t_logits, const int64_t*
                       float* row_ce, float* row_kl, int32_t* counts, void* stream);
 
 /* ---- embeddings (TF:modeling_whisper.py:675-676, 736-762) ------------------------------------------------------
- * out[b*T+t][:] = tok[ids[b*T+t]][:] + pos[t][:]; tables f32 or bf16 (tab_dtype); out f32 or bf16. */
+ * out[b*T+t][:] = tok[ids[b*T+t]][:] + pos[t][:]; tables f32 or bf16 (tab_dtype); out f32 or bf16.
+ * D a multiple of 4; tok, pos and out aligned to four of their elements (8 bytes for bf16, 16 for f32), DW_EINVAL otherwise.
+ * 0 <= ids < rows of tok is the caller's promise. */
 int dw_embed_fwd(const int64_t* ids, const void* tok, const void* pos, int tab_dtype, void* out, int out_dtype,
                  int B, int T, int D, void* stream);
 /* dtok[ids[r]] += dx[r] (atomic f32), dpos[t] += sum_b dx[b*T+t] (skipped if dpos NULL). */
@@ -202,11 +206,14 @@ int dw_embed_bwd(const float* dx, const int64_t* ids, float* dtok, float* dpos, 
  * conv1 (k3,p1,s1) and conv2 (k3,p1,s2) run as im2col + dw_gemm_bf16 with W' [D][3*C] (W'[d][k*C+c] = W[d][c][k]).
  * im2col_mel: mel f32 [B][C][T] -> xcol bf16 [B*T][kpad], xcol[(b,t)][k*C+c] = mel[b][c][t+k-1], zero padded. */
 int dw_im2col_mel(const float* mel, void* xcol, int B, int C, int T, int kpad, void* stream);
-/* im2col_s2: a bf16 [B*T][C] -> xcol bf16 [B*T/2][3*C], xcol[(b,t)][k*C+c] = a[b][2t+k-1][c]. */
+/* im2col_s2: a bf16 [B*T][C] -> xcol bf16 [B*T/2][3*C], xcol[(b,t)][k*C+c] = a[b][2t+k-1][c].
+ * T even, C a multiple of 8, a and xcol 16-byte aligned (eight bf16 per lane); DW_EINVAL otherwise. */
 int dw_im2col_s2(const void* a, void* xcol, int B, int T, int C, void* stream);
-/* col2im_s2 + GELU backward: dz[b][r][c] = gelu'(z[b][r][c]) * sum_{2t+k-1=r} dxcol[(b,t)][k*C+c]. */
+/* col2im_s2 + GELU backward: dz[b][r][c] = gelu'(z[b][r][c]) * sum_{2t+k-1=r} dxcol[(b,t)][k*C+c].
+ * T even, C a multiple of 8, dxcol, z and dz 16-byte aligned (eight bf16 per lane); DW_EINVAL otherwise. */
 int dw_col2im_s2_gelu_bwd(const void* dxcol, const void* z, void* dz, int B, int T, int C, void* stream);
-/* dz = bf16(dy) * gelu'(z): backward of the GELU after conv2 (dy f32 or bf16, z/dz bf16, n %% 4 == 0). */
+/* dz = bf16(dy) * gelu'(z): backward of the GELU after conv2 (dy f32 or bf16, z/dz bf16, n %% 4 == 0).
+ * z, dz and a bf16 dy 8-byte aligned, an f32 dy 16-byte aligned (four elements per lane); DW_EINVAL otherwise. */
 int dw_gelu_bwd(const void* dy, int dy_dtype, const void* z, void* dz, int64_t n, void* stream);
 /* conv weight <-> GEMM weight layouts: w [D][C][3] f32 <-> wp [D][kpad] (bf16 pack / f32 grad unpack-accumulate). */
 int dw_pack_conv_weight(const float* w, void* wp_bf16, int D, int C, int kpad, void* stream);
