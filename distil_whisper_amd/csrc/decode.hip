@@ -732,9 +732,32 @@ static int launch_decode_proj_ni(const DecAttnP& p, const dim3& grid, const dim3
     return DW_OK;
 }
 static bool decode_proj_dim_ok(int D) { return D == 384 || D == 512 || D == 768 || D == 1024 || D == 1280; }
-static int launch_decode_proj(int mode, int x_dtype, const DecAttnP& p, int B, int H, hipStream_t s) {
+// The one dispatch of attn_decode_proj_kernel (include/dwamd.h): decode_pass calls it for both of its attention blocks, the tests
+// call it alone.  Every refusal comes before the launch.
+extern "C" int dw_decode_attn_proj(int mode, const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps,
+                                   const void* w, const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows,
+                                   void* kv_app, void* o, int64_t ldo, int B, int H, int Lk, float scale, void* stream) {
+    DW_CLEAR_ERR();
+    if (mode != 0 && mode != 1) return DW_EINVAL;
+    if (x_dtype != DW_F32 && x_dtype != DW_BF16) return DW_EINVAL;
+    if (!x || !ln_g || !ln_b || !w || !bias || !k || !v || !o || (mode == 1 && !kv_app)) return DW_EINVAL;
+    if (B <= 0 || H <= 0 || Lk < 1 || Lk > kv_rows) return DW_EINVAL;
+    // 16-byte loads: the row of x, the weight fragments, the key / value groups, four floats of gamma / beta per lane
+    if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)k | (uintptr_t)v | (uintptr_t)ln_g | (uintptr_t)ln_b) & 15) || (ldx & 7) || (ldkv & 7))
+        return DW_EINVAL;
+    if (((uintptr_t)bias & 3) || ((uintptr_t)o & 1) || (mode == 1 && ((uintptr_t)kv_app & 1))) return DW_EINVAL;
+    if (B > 65535 || H > 65535 || !decode_proj_dim_ok(H * 64) || Lk > 8192) return DW_EUNSUP;
+    const int D = H * 64;
+    if (ldx < D || ldo < D || ldkv < (mode == 1 ? 2L * D : (long)D)) return DW_EINVAL;
+    DecAttnP p = {};
+    p.x = x; p.ldx = ldx; p.ln_g = ln_g; p.ln_b = ln_b; p.eps = eps;
+    p.w = (const bf16*)w; p.bias = bias;
+    p.k = (const bf16*)k; p.v = (const bf16*)v; p.ldkv = ldkv; p.kv_rows = kv_rows;
+    p.kv_app = mode == 1 ? (bf16*)kv_app : nullptr; p.o = (bf16*)o; p.ldo = ldo;
+    p.D = D; p.Lk = Lk; p.t = mode == 1 ? Lk - 1 : 0; p.scale = scale;
     const size_t smem = ((((size_t)p.Lk + 3) & ~(size_t)3) + DEC_NW * 64 + 3 * DEC_NW + 3 * 64) * 4 + (size_t)p.D * 6;
     const dim3 grid(1, H, B), block(64 * DEC_NW);
+    const hipStream_t s = (hipStream_t)stream;
     const bool xbf = x_dtype == DW_BF16;
     if (mode == 0 && xbf) return launch_decode_proj_ni<0, true>(p, grid, block, smem, s);
     if (mode == 0) return launch_decode_proj_ni<0, false>(p, grid, block, smem, s);
@@ -1038,12 +1061,9 @@ static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void*
         if (!L.wqkv || !L.wo || !L.wq || !L.wo2 || !L.w1 || !L.w2 || !L.self_kv || !L.cross_kv) return DW_EINVAL;
         // ---- self-attention over the cached prefix ----
         if (proj_self && L.bqkv && L.ln1_g && L.ln1_b) {
-            DecAttnP q = {};
-            q.x = d->x; q.ldx = D; q.ln_g = L.ln1_g; q.ln_b = L.ln1_b; q.eps = 1e-5f;
-            q.w = (const bf16*)L.wqkv; q.bias = L.bqkv;
-            q.k = (const bf16*)L.self_kv; q.v = q.k + D; q.ldkv = 2 * D; q.kv_rows = d->max_len;
-            q.kv_app = (bf16*)L.self_kv; q.o = (bf16*)d->o; q.ldo = D; q.D = D; q.Lk = t + 1; q.t = t; q.scale = 0.125f;
-            if ((rc = launch_decode_proj(1, d->stream_dtype, q, B, H, (hipStream_t)stream)) != DW_OK) return rc;
+            const bf16* kc0 = (const bf16*)L.self_kv;
+            if ((rc = dw_decode_attn_proj(1, d->x, d->stream_dtype, D, L.ln1_g, L.ln1_b, 1e-5f, L.wqkv, L.bqkv, kc0, kc0 + D, 2L * D,
+                                          d->max_len, L.self_kv, d->o, D, B, H, t + 1, 0.125f, stream)) != DW_OK) return rc;
         } else {
         if (fuse_ln) {
             rc = gemm(d->x, D, L.wqkv, L.bqkv, 3 * D, D, d->qkv, 3 * D, DW_BF16, 0, nullptr, L.ln1_g, L.ln1_b,
@@ -1078,12 +1098,9 @@ static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void*
             return rc;
         // ---- cross-attention over the static encoder K/V ----
         if (proj_cross && L.bq && L.ln2_g && L.ln2_b) {
-            DecAttnP q = {};
-            q.x = d->x; q.ldx = D; q.ln_g = L.ln2_g; q.ln_b = L.ln2_b; q.eps = 1e-5f;
-            q.w = (const bf16*)L.wq; q.bias = L.bq;
-            q.k = (const bf16*)L.cross_kv; q.v = q.k + D; q.ldkv = ldx; q.kv_rows = d->src_len;
-            q.o = (bf16*)d->o; q.ldo = D; q.D = D; q.Lk = d->src_len; q.t = 0; q.scale = 0.125f;
-            if ((rc = launch_decode_proj(0, d->stream_dtype, q, B, H, (hipStream_t)stream)) != DW_OK) return rc;
+            const bf16* kx0 = (const bf16*)L.cross_kv;
+            if ((rc = dw_decode_attn_proj(0, d->x, d->stream_dtype, D, L.ln2_g, L.ln2_b, 1e-5f, L.wq, L.bq, kx0, kx0 + D, ldx, d->src_len,
+                                          nullptr, d->o, D, B, H, d->src_len, 0.125f, stream)) != DW_OK) return rc;
         } else {
         if (fuse_ln) {
             rc = gemm(d->x, D, L.wq, L.bq, D, D, d->qkv, 3 * D, DW_BF16, 0, nullptr, L.ln2_g, L.ln2_b, nullptr);

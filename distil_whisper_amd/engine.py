@@ -915,7 +915,9 @@ class WhisperEngine:
         tests runs it).  `dw_decode_step` computes the same pass in fewer launches: since round 5 it runs LayerNorm + q
         projection + cross-attention in ONE kernel (`attn_decode_proj_kernel`, dw_debug_set key 7, default 4), whose fp32
         summation order differs from the GEMV's -- q may differ by one bf16 ulp between the two paths.  Tests that
-        compare them either pin `dw_debug_set(7, 12)` (the unfused sequence: exactly this one) or state a tolerance.
+        compare them either pin `dw_debug_set(7, 12)` (the unfused sequence: exactly this one) or state a tolerance: the
+        tests that state one are tests/test_decode_edges_gpu.py (the kernel alone through `dw_decode_attn_proj`, and whole
+        passes under key 7 = 0 / 4 / 8 / 12, bounded per row against float64) and tests/test_decode_parity_large.py.
         row_t (a list of B ints; `decode_multi_rows`): row b starts at position row_t[b] instead of cache["t"] -- its K/V go to
         the cache rows row_t[b] + j by indexing and its self-attention is one `ops.attn_fwd` call over its own row_t[b] + n keys."""
         ops, st, d = self.ops, self.st, self.dims

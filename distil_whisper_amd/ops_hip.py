@@ -54,6 +54,9 @@ _SIGS = {
     "dw_version": ([], C.c_int),
     "dw_decode_step": ([C.POINTER(DwDecodeStep), C.c_void_p], C.c_int),
     "dw_decode_step_rows": ([C.POINTER(DwDecodeStep), C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
+    "dw_decode_attn_proj": ([C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                             C.c_float, C.c_void_p], C.c_int),
     "dw_logmel": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                    C.c_void_p], C.c_int),
     "dw_gemm_bf16": ([C.POINTER(DwGemm), C.c_void_p], C.c_int),
@@ -406,6 +409,21 @@ class HipOps:
         e0 = self._t0()
         self._chk(self.lib.dw_decode_step_rows(C.byref(desc), _p(row_t), int(max_t), self._stream()), "decode_step_rows")
         self._t1(e0, "decode_step_rows", 0.0)
+
+    def decode_attn_proj(self, mode, x, ln_g, ln_b, w, bias, k, v, B, H, Lk, *, kv_rows=None, kv_app=None, eps=1e-5, scale=0.125,
+                         out=None):
+        """The token step's attention with its projection inside, alone (dw_decode_attn_proj, the launch dw_decode_step makes):
+        mode 0 LayerNorm + q projection + attention over the Lk keys of k / v, mode 1 q / k / v projection, the new K | V written
+        to row Lk - 1 of every sequence in `kv_app`, attention over the Lk - 1 rows in front of it and the new key.  x [B, D] f32 or
+        bf16; k, v: 2-D views with one row pitch, `kv_rows` rows per sequence (default Lk).  Thin: the library checks the
+        arguments (include/dwamd.h)."""
+        o = self.empty((B, H * 64), torch.bfloat16) if out is None else out
+        e0 = self._t0()
+        self._chk(self.lib.dw_decode_attn_proj(int(mode), _p(x), _dt(x), x.stride(0), _p(ln_g), _p(ln_b), float(eps), _p(w), _p(bias),
+                                               _p(k), _p(v), k.stride(0), Lk if kv_rows is None else int(kv_rows), _p(kv_app),
+                                               _p(o), o.stride(0), B, H, int(Lk), float(scale), self._stream()), "decode_attn_proj")
+        self._t1(e0, "decode_attn_proj", 0.0)
+        return o
 
     def layernorm_fwd(self, x, gamma, beta, eps=1e-5, save_stats=True, out=None):
         """x, out: 2-D with unit column stride; their row pitches may exceed the row length (padded activation buffers)."""

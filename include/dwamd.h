@@ -493,6 +493,30 @@ int dw_decode_step(const DwDecodeStep* d, void* stream);
  * DW_EUNSUP.  DW_EINVAL: what dw_decode_step refuses, a null or misaligned row_t, max_t < 0, max_t + n_new > max_len.  Refused
  * calls launch nothing.  Nothing is allocated, nothing synchronises. */
 int dw_decode_step_rows(const DwDecodeStep* d, const int32_t* row_t, int32_t max_t, void* stream);
+/* dw_decode_attn_proj: the token step's attention with its projection inside, alone -- the one launch dw_decode_step makes for a
+ * layer's cross-attention (mode 0; dw_debug_set key 7 bit 3 clear) or self-attention (mode 1; bit 2 clear), through this very
+ * function.  Per sequence b < B and head h < H (D = 64 * H), one workgroup:
+ *   ln   = bf16(LayerNorm(x[b]; ln_g, ln_b, eps))                     x: [B] rows of D, x_dtype DW_F32 / DW_BF16, ldx elements apart
+ *   mode 0:  q = bf16(w[h] . ln + bias[h])                            w bf16 [D][D], bias f32 [D]
+ *            o[b][h] = softmax_j(scale * q . k[b][j][h]) v[b][j][h]   over the Lk keys j of k / v
+ *   mode 1:  q, k_new, v_new the same way from w bf16 [3D][D] (q | k | v stacked), bias f32 [3D]; k_new | v_new are written to
+ *            columns [0, D) | [D, 2D) of row t = Lk - 1 of sequence b in kv_app, and the softmax runs over the Lk - 1 rows of k / v
+ *            in front of t and the new key, which is not read back from memory (Lk = 1: no key is read at all).
+ * k, v: bf16, head h at element offset 64 * h, key j of sequence b at row b * kv_rows + j, rows ldkv elements apart (k and v are
+ * usually two column offsets into one K | V buffer).  kv_app: bf16, same pitches (ldkv >= 2D), may be the buffer k points into;
+ * ignored in mode 0.  o: bf16 [B][ldo].  fp32 sums over bf16 operands, P rounded to bf16 in front of the PV product.
+ * Checked before any launch, in this order:
+ *   DW_EINVAL  mode not 0 / 1; x_dtype not DW_F32 / DW_BF16; a null x, ln_g, ln_b, w, bias, k, v, o (kv_app in mode 1);
+ *              B < 1, H < 1, Lk < 1, Lk > kv_rows;
+ *              x, w, k, v, ln_g or ln_b not 16-byte aligned, ldx or ldkv not a multiple of 8 elements (the kernel issues 16-byte
+ *              loads on all of them); bias not 4-byte, o / kv_app not 2-byte aligned
+ *   DW_EUNSUP  B or H above 65535 (grid dimensions); D = 64 * H not one of 384 / 512 / 768 / 1024 / 1280 (the instantiations: a
+ *              lane holds a weight row's fragments in registers); Lk > 8192 (one score per key in LDS)
+ *   DW_EINVAL  ldx < D, ldo < D, ldkv < D (mode 1: < 2D)
+ * A refused call launches nothing and writes nothing.  One launch on `stream`; nothing is allocated, nothing synchronises. */
+int dw_decode_attn_proj(int mode, const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps,
+                        const void* w, const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows,
+                        void* kv_app, void* o, int64_t ldo, int B, int H, int Lk, float scale, void* stream);
 
 /* ---- token-level timestamps (TF:generation_whisper.py:241-381 `_extract_token_timestamps`, :43-61 `_median_filter`, :64-115
  * `_dynamic_time_warping`; reached from `generate(return_token_timestamps=True)`, TF:1146-1157).  The reference collects every

@@ -146,7 +146,11 @@ def test_decode_family_eager_equals_graph_replay_gpu():
 def test_decode_fixtures_under_every_token_step_fusion_mode_gpu(fuse_off):
     """dw_debug_set key 7: 4 is the default (cross-attention with its q projection inside, self-attention as separate launches);
     0 adds the self-attention kernel with its q / k / v projection and cache append inside (measured slower, kept behind the
-    switch), 8 / 12 are the separate-launch forms.  Every mode must reproduce the reference's tokens."""
+    switch), 8 / 12 are the separate-launch forms.  What this covers: the fixtures' models have d_model 128, which is none of the
+    widths `attn_decode_proj_kernel` is instantiated for (384 / 512 / 768 / 1024 / 1280), so bits 2 and 3 of the key change no
+    launch here -- every value runs the separate-launch sequence, and the test pins that setting the key leaves that sequence and
+    its tokens alone.  The kernel itself, under each value of the key and at each of its widths, is judged by
+    tests/test_decode_edges_gpu.py."""
     ops = _ops("hip")
     assert ops.lib.dw_debug_set(7, fuse_off) == 0
     try:
