@@ -500,6 +500,8 @@ extern "C" int dw_sample_select(const void* logits, int B, int V, int64_t ld, co
 // Same arithmetic as the separate launches: two-pass LayerNorm statistics, bf16 operands, fp32 sums (in another order than the
 // MFMA GEMV's -- a q element may differ by one bf16 ulp), P rounded to bf16 in front of the PV product.
 // ---------------------------------------------------------------------------------------------------------------------
+// a row's position from the device array of the per-row passes (further down), clamped to the host's bound [0, max_t]
+__device__ __forceinline__ int row_pos(const int32_t* row_t, long b, int max_t) { return min(max(row_t[b], 0), max_t); }
 struct DecAttnP {
     const void* x; long ldx;                   // residual stream [B][D] (f32 or bf16)
     const float* ln_g; const float* ln_b; float eps;
@@ -510,6 +512,7 @@ struct DecAttnP {
     bf16* o; long ldo;
     int D, Lk, t;                              // Lk counts the new key in MODE 1 (= t + 1)
     float scale;
+    const int32_t* row_t; int max_t;           // ROWS (MODE 1): sequence b stands at row_t[b] <= max_t; Lk = max_t + 1 places the LDS regions
 };
 template <bool XBF>
 __device__ __forceinline__ void dec_ld_x8(const void* x, long off, float (&v)[8]) {
@@ -524,7 +527,10 @@ __device__ __forceinline__ void dec_ld_x8(const void* x, long off, float (&v)[8]
     }
 }
 constexpr int DEC_NW = 8;                      // waves per workgroup (two workgroups per CU at <= 128 registers)
-template <int MODE, bool XBF, int NI>        // NI = D / 64: 64-column steps of a weight row (compile time: the fragments live in registers)
+// ROWS (MODE 1, dw_decode_attn_proj_rows): the sequence's own position from p.row_t in place of the uniform p.t / p.Lk -- the
+// workgroup of (b, h) then does what the uniform kernel does at Lk = row_t[b] + 1, sum for sum; p.Lk = max_t + 1 only places the
+// scratch regions behind the scores in LDS.
+template <int MODE, bool XBF, int NI, bool ROWS = false>   // NI = D / 64: 64-column steps of a weight row (compile time: the fragments live in registers)
 __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const DecAttnP p) {
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     // [Lk scores (x4) | NW x 64 partial outputs | NW | NW | NW (sums) | 64 q | 64 k_new | 64 v_new | D bf16 normalised row | D f32 row]
@@ -532,6 +538,9 @@ __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = blockIdx.y, b = blockIdx.z;
     constexpr int D = NI * 64;
+    static_assert(!ROWS || MODE == 1, "per-row positions belong to the self-attention");
+    const int Lk = ROWS ? __builtin_amdgcn_readfirstlane(row_pos(p.row_t, b, p.max_t)) + 1 : p.Lk;   // keys of this sequence
+    const int t_app = ROWS ? Lk - 1 : p.t;
     float* sc = dsm;
     float* part = dsm + ((p.Lk + 3) & ~3);
     float* redm = part + DEC_NW * 64;
@@ -622,7 +631,7 @@ __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const 
             if (l == 0) {
                 const bf16 r = f2bf(a + p.bias[part_i * D + h * 64 + j]);
                 (part_i == 1 ? knew : vnew)[j] = bf2f(r);
-                p.kv_app[((long)b * p.kv_rows + p.t) * p.ldkv + (part_i - 1) * D + h * 64 + j] = r;
+                p.kv_app[((long)b * p.kv_rows + t_app) * p.ldkv + (part_i - 1) * D + h * 64 + j] = r;
             }
         }
     }
@@ -634,10 +643,10 @@ __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const 
     float qv[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) qv[e] = qs[ds + e];
-    const int nold = MODE == 1 ? p.Lk - 1 : p.Lk;        // keys that live in memory
+    const int nold = MODE == 1 ? Lk - 1 : Lk;        // keys that live in memory
     constexpr int UN = 8;                                // key groups requested ahead per lane
     float mx = NEG_BIG_D;
-    for (int k0 = wave * 8; k0 < p.Lk; k0 += UN * DEC_NW * 8) {
+    for (int k0 = wave * 8; k0 < Lk; k0 += UN * DEC_NW * 8) {
         bf16x8 kr[UN];
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
@@ -659,7 +668,7 @@ __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const 
             s += __shfl_xor(s, 1);
             s += __shfl_xor(s, 2);
             s += __shfl_xor(s, 4);
-            if (k < p.Lk) {
+            if (k < Lk) {
                 if ((lane & 7) == 0) sc[k] = s;
                 mx = fmaxf(mx, s);
             }
@@ -673,7 +682,7 @@ __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const 
     for (int i = 1; i < DEC_NW; ++i) mx = fmaxf(mx, redm[i]);
     float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float lsum = 0.f;
-    for (int k0 = wave * 8; k0 < p.Lk; k0 += UN * DEC_NW * 8) {
+    for (int k0 = wave * 8; k0 < Lk; k0 += UN * DEC_NW * 8) {
         bf16x8 vr[UN];
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
@@ -684,7 +693,7 @@ __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const 
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int k = k0 + u * DEC_NW * 8 + sub;
-            if (k < p.Lk) {
+            if (k < Lk) {
                 const float pv = __builtin_amdgcn_exp2f(sc[k] - mx);
                 lsum += pv;
                 const float pb = round_bf16(pv);
@@ -720,10 +729,10 @@ __global__ __launch_bounds__(64 * DEC_NW, 4) void attn_decode_proj_kernel(const 
     }
 }
 
-template <int MODE, bool XBF>
+template <int MODE, bool XBF, bool ROWS = false>
 static int launch_decode_proj_ni(const DecAttnP& p, const dim3& grid, const dim3& block, size_t smem, hipStream_t s) {
     switch (p.D >> 6) {
-#define DW_NI(n) case n: hipLaunchKernelGGL((attn_decode_proj_kernel<MODE, XBF, n>), grid, block, smem, s, p); break;
+#define DW_NI(n) case n: hipLaunchKernelGGL((attn_decode_proj_kernel<MODE, XBF, n, ROWS>), grid, block, smem, s, p); break;
         DW_NI(6) DW_NI(8) DW_NI(12) DW_NI(16) DW_NI(20)        // d_model 384 / 512 / 768 / 1024 / 1280
 #undef DW_NI
         default: return DW_EINVAL;
@@ -734,11 +743,13 @@ static int launch_decode_proj_ni(const DecAttnP& p, const dim3& grid, const dim3
 static bool decode_proj_dim_ok(int D) { return D == 384 || D == 512 || D == 768 || D == 1024 || D == 1280; }
 // The one dispatch of attn_decode_proj_kernel (include/dwamd.h): decode_pass calls it for both of its attention blocks, the tests
 // call it alone.  Every refusal comes before the launch.
-extern "C" int dw_decode_attn_proj(int mode, const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps,
-                                   const void* w, const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows,
-                                   void* kv_app, void* o, int64_t ldo, int B, int H, int Lk, float scale, void* stream) {
-    DW_CLEAR_ERR();
+// rows: the per-row entry (dw_decode_attn_proj_rows); Lk is then max_t + 1, so the refusals by Lk bound every row's key count.
+static int decode_attn_proj(int mode, const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps,
+                            const void* w, const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows,
+                            void* kv_app, void* o, int64_t ldo, int B, int H, int Lk, float scale, bool rows, const int32_t* row_t,
+                            void* stream) {
     if (mode != 0 && mode != 1) return DW_EINVAL;
+    if (rows && (mode != 1 || !row_t || ((uintptr_t)row_t & 3))) return DW_EINVAL;
     if (x_dtype != DW_F32 && x_dtype != DW_BF16) return DW_EINVAL;
     if (!x || !ln_g || !ln_b || !w || !bias || !k || !v || !o || (mode == 1 && !kv_app)) return DW_EINVAL;
     if (B <= 0 || H <= 0 || Lk < 1 || Lk > kv_rows) return DW_EINVAL;
@@ -755,14 +766,35 @@ extern "C" int dw_decode_attn_proj(int mode, const void* x, int x_dtype, int64_t
     p.k = (const bf16*)k; p.v = (const bf16*)v; p.ldkv = ldkv; p.kv_rows = kv_rows;
     p.kv_app = mode == 1 ? (bf16*)kv_app : nullptr; p.o = (bf16*)o; p.ldo = ldo;
     p.D = D; p.Lk = Lk; p.t = mode == 1 ? Lk - 1 : 0; p.scale = scale;
+    p.row_t = row_t; p.max_t = Lk - 1;
     const size_t smem = ((((size_t)p.Lk + 3) & ~(size_t)3) + DEC_NW * 64 + 3 * DEC_NW + 3 * 64) * 4 + (size_t)p.D * 6;
     const dim3 grid(1, H, B), block(64 * DEC_NW);
     const hipStream_t s = (hipStream_t)stream;
     const bool xbf = x_dtype == DW_BF16;
+    if (rows) return xbf ? launch_decode_proj_ni<1, true, true>(p, grid, block, smem, s) : launch_decode_proj_ni<1, false, true>(p, grid, block, smem, s);
     if (mode == 0 && xbf) return launch_decode_proj_ni<0, true>(p, grid, block, smem, s);
     if (mode == 0) return launch_decode_proj_ni<0, false>(p, grid, block, smem, s);
     if (xbf) return launch_decode_proj_ni<1, true>(p, grid, block, smem, s);
     return launch_decode_proj_ni<1, false>(p, grid, block, smem, s);
+}
+extern "C" int dw_decode_attn_proj(int mode, const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps,
+                                   const void* w, const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows,
+                                   void* kv_app, void* o, int64_t ldo, int B, int H, int Lk, float scale, void* stream) {
+    DW_CLEAR_ERR();
+    return decode_attn_proj(mode, x, x_dtype, ldx, ln_g, ln_b, eps, w, bias, k, v, ldkv, kv_rows, kv_app, o, ldo, B, H, Lk, scale, false,
+                            nullptr, stream);
+}
+// Mode 1 with sequence b at its own position row_t[b] (device int32 [B], clamped to [0, max_t] by the kernel; the host never reads
+// it): the new K/V go to cache row row_t[b] and the softmax runs over row_t[b] + 1 keys.  The refusals of the uniform entry with
+// Lk = max_t + 1, in front of the launch.
+extern "C" int dw_decode_attn_proj_rows(const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps,
+                                        const void* w, const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows,
+                                        void* kv_app, void* o, int64_t ldo, int B, int H, float scale, const int32_t* row_t,
+                                        int32_t max_t, void* stream) {
+    DW_CLEAR_ERR();
+    if (max_t < 0 || (int64_t)max_t + 1 > kv_rows) return DW_EINVAL;
+    return decode_attn_proj(1, x, x_dtype, ldx, ln_g, ln_b, eps, w, bias, k, v, ldkv, kv_rows, kv_app, o, ldo, B, H, max_t + 1, scale, true,
+                            row_t, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -796,7 +828,6 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16* qkv, bf16* c
 // row_t is device memory that only these three kernels read; each clamps it to [0, max_t], the host's bound that the caller
 // checked against the cache (max_t + n <= max_len): a stale or wild entry cannot reach past a row's own cache.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int row_pos(const int32_t* row_t, long b, int max_t) { return min(max(row_t[b], 0), max_t); }
 
 // embed_fwd_kernel (elementwise.hip) with the position row taken per sequence: x[b * n + j] = tok[ids[b][j]] + pos[row_t[b] + j],
 // the sum in fp32, rounded once where the stream is bf16.  BF: tables and stream bf16, else both f32 (DwDecodeStep.stream_dtype).
@@ -991,7 +1022,8 @@ __global__ __launch_bounds__(AR_NT) void attn_rows_kernel(const bf16* qkv, long 
 // The pass of dw_decode_step (row_t == nullptr: every row starts at d->t) and of dw_decode_step_rows (row b starts at row_t[b] <=
 // max_t, a device array the host never reads: `t` is then max_t and sizes launches only).  The rows pass swaps three launches --
 // embedding, K/V append, self-attention (the *_rows kernels above) -- and keeps every other launch of the uniform pass.
-static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void* stream) {
+// token_rows (dw_decode_token_rows, n_new == 1): the rows pass keeps the self-attention with its projection inside, at per-row positions.
+static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void* stream, bool token_rows = false) {
     const int B = d->batch, n = d->n_new, D = d->d_model, H = d->heads, F = d->ffn;
     if (B <= 0 || n <= 0 || D != H * 64 || (D & 63) || (F & 63) || d->n_layers <= 0 || d->src_len <= 0 || t < 0 ||
         t + n > d->max_len || d->ldv < d->vocab || (d->ldv & 15))
@@ -1034,7 +1066,7 @@ static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void*
     const bool fuse_kv = !row_t && rows <= 64 && !(g_decode_fuse_off & 2);
     // token step: the q (q / k / v) projection of a head is computed by the attention workgroup of that head
     const bool proj_ok = n == 1 && decode_proj_dim_ok(D);
-    const bool proj_self = !row_t && proj_ok && !(g_decode_fuse_off & 4) && t + 1 <= 8192;
+    const bool proj_self = (!row_t || token_rows) && proj_ok && !(g_decode_fuse_off & 4) && t + 1 <= 8192;
     const bool proj_cross = proj_ok && !(g_decode_fuse_off & 8) && d->src_len <= 8192;
     auto gemm = [&](const void* a, long lda, const void* w, const float* bias, int N, int K, void* c, long ldc, int c_dtype,
                     int act, const void* r, const float* ln_g, const float* ln_b, void* kv) -> int {
@@ -1062,8 +1094,9 @@ static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void*
         // ---- self-attention over the cached prefix ----
         if (proj_self && L.bqkv && L.ln1_g && L.ln1_b) {
             const bf16* kc0 = (const bf16*)L.self_kv;
-            if ((rc = dw_decode_attn_proj(1, d->x, d->stream_dtype, D, L.ln1_g, L.ln1_b, 1e-5f, L.wqkv, L.bqkv, kc0, kc0 + D, 2L * D,
-                                          d->max_len, L.self_kv, d->o, D, B, H, t + 1, 0.125f, stream)) != DW_OK) return rc;
+            if ((rc = decode_attn_proj(1, d->x, d->stream_dtype, D, L.ln1_g, L.ln1_b, 1e-5f, L.wqkv, L.bqkv, kc0, kc0 + D, 2L * D,
+                                       d->max_len, L.self_kv, d->o, D, B, H, t + 1, 0.125f, row_t != nullptr, row_t, stream)) != DW_OK)
+                return rc;
         } else {
         if (fuse_ln) {
             rc = gemm(d->x, D, L.wqkv, L.bqkv, 3 * D, D, d->qkv, 3 * D, DW_BF16, 0, nullptr, L.ln1_g, L.ln1_b,
@@ -1145,4 +1178,13 @@ extern "C" int dw_decode_step_rows(const DwDecodeStep* d, const int32_t* row_t, 
     DW_CLEAR_ERR();
     if (!decode_desc_ok(d) || !row_t || ((uintptr_t)row_t & 3)) return DW_EINVAL;
     return decode_pass(d, row_t, max_t, stream);
+}
+
+// The token step (n_new == 1) with row b at position row_t[b]: the launches of dw_decode_step with the embedding and the
+// self-attention taken per row (embed_rows_kernel, attn_decode_proj_kernel<1, ., ., true>).  Where the width has no such kernel or
+// dw_debug_set key 7 has the self-attention fusion off, the pass of dw_decode_step_rows.
+extern "C" int dw_decode_token_rows(const DwDecodeStep* d, const int32_t* row_t, int32_t max_t, void* stream) {
+    DW_CLEAR_ERR();
+    if (!decode_desc_ok(d) || !row_t || ((uintptr_t)row_t & 3) || d->n_new != 1) return DW_EINVAL;
+    return decode_pass(d, row_t, max_t, stream, true);
 }

@@ -441,6 +441,174 @@ class GreedyDecoder:
         return self.tokens[:, :n].clone()
 
 
+def slot_step_torch(logits, V, tokens, length, plen, budget, done, row_t, cur, *, suppress=None, begin_suppress=None,
+                    timestamp_rules=None, eos=None, min_new=0):
+    """The slot step of continuous batching as torch ops and host arithmetic (`dw_slot_step`, csrc/slots.hip, is the kernel;
+    include/dwamd.h states the rule): the path of oracle.ref_ops and the CPU.  logits [S, >= V]: row b is the output of the pass
+    that fed cur[b] at position row_t[b]; tokens int64 [S, max_len]; length / plen / budget / row_t int32 [S]; done bool [S]; cur
+    int64 [S, 1]; all updated in place.  A done slot is parked at position 0; inside its prompt a slot takes the forced token;
+    otherwise the argmax of `processed_scores` with the slot's own history, begin_index = plen[b], first = (len == plen), no_eos =
+    (len - plen < min_new); a generated EOS or a spent budget ends the slot."""
+    lens, pls, buds, dns = length.tolist(), plen.tolist(), budget.tolist(), done.tolist()
+    rules = None if timestamp_rules is None else dict(timestamp_rules)
+    for b in range(tokens.shape[0]):
+        n, P = lens[b], pls[b]
+        if dns[b] or n < 1 or n >= tokens.shape[1] or P < 1:
+            done[b] = True
+            row_t[b] = 0
+            cur[b, 0] = tokens[b, 0]
+            continue
+        forced = n < P
+        if forced:
+            nxt = int(tokens[b, n])
+        else:
+            sc = processed_scores(logits[b:b + 1, :V], tokens[b:b + 1], n, begin_index=P, eos=eos, no_eos=n - P < int(min_new),
+                                  first=n == P, suppress=suppress, begin_suppress=begin_suppress, timestamp_rules=rules)
+            nxt = int(sc.argmax(-1))
+        tokens[b, n] = nxt
+        length[b] = n + 1
+        if not forced and ((eos is not None and nxt == eos) or n + 1 >= buds[b]):
+            done[b] = True
+            row_t[b] = 0
+            cur[b, 0] = tokens[b, 0]
+        else:
+            row_t[b] = n
+            cur[b, 0] = nxt
+
+
+class SlotDecoder:
+    """Continuous batching of greedy decoding: `slots` rows of one token loop, each at its own position of its own window; a row
+    that has produced EOS (or spent its budget) hands its slot to the next waiting window instead of idling until the longest row
+    of a batch is done.  Tokens are those of `GreedyDecoder` for the same window: the same rules, the same token step.
+
+    A step is `engine.decode_token_rows` (dw_decode_token_rows: the token step with every row at its own position, fed from the
+    device arrays `cur` / `row_t`) plus the slot step (`ops.slot_step`, dw_slot_step; `slot_step_torch` on ops without it), which
+    selects every slot's token from the slot's own state (len, prompt length, budget, done) and writes the next feed.  Neither
+    takes a host argument that depends on a position except the bound `max_t`, which only sizes LDS; with `use_graphs` the pair is
+    captured once per bucket of 64 positions of that bound and replayed.  Every `check_every` steps the host reads `done` and `len`
+    -- the only synchronisation --, yields the finished rows and refills their slots: the window's encoder rows are projected into
+    the slot's cross-attention K/V (`engine.decode_refill`) and its prompt is teacher-forced one token per step like any other
+    position.  The host's bound of `max_t` is the largest `len - 1` it last read (0 for a fresh slot) plus the steps since.
+
+    run(windows): `windows` iterates (key, enc_rows, prompt_ids, max_new_tokens) -- enc_rows: the window's encoder output rows
+    (engine layout), prompt_ids: P >= 1 ids (list or 1-D tensor), max_new_tokens >= 1 with P + max_new_tokens <= max_len.  Yields
+    (key, row) as rows finish, row int64 = prompt + generated tokens up to and including EOS.  `steps` counts executed token steps."""
+    BUCKET = 64
+
+    def __init__(self, engine, slots, max_len, eos_token_id, suppress_tokens=None, begin_suppress_tokens=None, timestamp_rules=None,
+                 min_new_tokens=0, pad_token_id=None, use_graphs=None, check_every=8):
+        self.eng, self.S, self.max_len = engine, int(slots), int(max_len)
+        d = engine.dims
+        if self.S < 1 or int(check_every) < 1:
+            raise ValueError("SlotDecoder needs at least one slot and check_every >= 1")
+        if self.max_len > d.max_tgt:
+            raise ValueError(f"max_len = {max_len} exceeds max_target_positions = {d.max_tgt}")
+        if eos_token_id is None:
+            raise ValueError("SlotDecoder needs eos_token_id: a slot is handed on when its row ends")
+        dev = engine.ops.device
+        self.dev, self.eos = dev, int(eos_token_id)
+        self.fill = self.eos if pad_token_id is None else int(pad_token_id)
+        self.min_new = int(min_new_tokens)
+        self.use_graphs = (torch.device(dev).type == "cuda" and hasattr(engine.ops, "slot_step")) if use_graphs is None else bool(use_graphs)
+        self.check_every = int(check_every)
+        self.timestamp_rules = timestamp_rules
+        self.suppress = token_mask(suppress_tokens, d.vocab, dev, torch.uint8)
+        self.begin_suppress = token_mask(begin_suppress_tokens, d.vocab, dev, torch.uint8)
+        S = self.S
+        self.tokens = torch.zeros((S, self.max_len), dtype=torch.long, device=dev)
+        self.cur = torch.zeros((S, 1), dtype=torch.long, device=dev)
+        self.done = torch.ones((S,), dtype=torch.bool, device=dev)
+        self.state = torch.ones((4, S), dtype=torch.int32, device=dev)          # rows: len, plen, budget, row_t
+        self.len, self.plen, self.budget, self.row_t = self.state[0], self.state[1], self.state[2], self.state[3]
+        self.cache = None
+        self.graphs = {}
+        self.pool = None
+        self._warm = False
+        self.steps = 0
+
+    def _step(self, max_t):
+        eng, V = self.eng, self.eng.dims.vocab
+        logits = eng.decode_token_rows(self.cur, self.cache, self.row_t, max_t)
+        r = self.timestamp_rules
+        if hasattr(eng.ops, "slot_step"):
+            mi = None if r is None else r.get("max_initial_timestamp_index")
+            eng.ops.slot_step(logits, V, self.tokens, self.len, self.plen, self.budget, self.done, self.row_t, self.cur,
+                              suppress=self.suppress, begin_suppress=self.begin_suppress,
+                              ts_begin=-1 if r is None else int(r["no_timestamps_token_id"]) + 1, max_initial=-1 if mi is None else int(mi),
+                              eos=self.eos, min_new=self.min_new)
+        else:
+            slot_step_torch(logits, V, self.tokens, self.len, self.plen, self.budget, self.done, self.row_t, self.cur,
+                            suppress=self.suppress, begin_suppress=self.begin_suppress, timestamp_rules=r, eos=self.eos,
+                            min_new=self.min_new)
+
+    def _run_step(self, bound):
+        # the pass is launched with the bucket's last position as max_t: it places the kernels' LDS regions only
+        bucket = bound // self.BUCKET
+        max_t = min((bucket + 1) * self.BUCKET, self.max_len) - 1
+        self.steps += 1
+        if not self.use_graphs:
+            self._step(max_t)
+            return
+        g = self.graphs.get(bucket)
+        if g is None:
+            if not self._warm:
+                # one eager step first: lazy initialisation inside torch must not happen under stream capture
+                keep = (self.cur.clone(), self.tokens.clone(), self.done.clone(), self.state.clone())
+                self._step(max_t)
+                self.cur.copy_(keep[0]); self.tokens.copy_(keep[1]); self.done.copy_(keep[2]); self.state.copy_(keep[3])
+                torch.cuda.synchronize(self.dev)
+                self.pool = torch.cuda.graph_pool_handle()
+                self._warm = True
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self.pool):
+                self._step(max_t)
+            self.graphs[bucket] = g
+        g.replay()
+
+    def _refill(self, b, enc_rows, prompt, max_new):
+        prompt = torch.as_tensor(prompt, dtype=torch.long).reshape(-1)
+        P, max_new = int(prompt.numel()), int(max_new)
+        if P < 1 or max_new < 1 or P + max_new > self.max_len:
+            raise ValueError(f"a window needs 1 <= prompt length, 1 <= max_new_tokens and prompt + max_new_tokens <= max_len = "
+                             f"{self.max_len} (got {P} + {max_new})")
+        self.eng.decode_refill(self.cache, b, enc_rows)
+        self.tokens[b, :P] = prompt.to(self.dev)
+        self.state[:, b] = torch.tensor([1, P, P + max_new, 0], dtype=torch.int32).to(self.dev)
+        self.cur[b, 0] = self.tokens[b, 0]
+        self.done[b] = False
+
+    def run(self, windows):
+        S = self.S
+        if self.cache is None:
+            self.cache = self.eng.decode_slots_init(S, self.max_len)
+        self.done.fill_(True)                         # every slot empty: parked until a window takes it
+        keys = [None] * S
+        it = iter(windows)
+        while True:
+            dn, ln = self.done.tolist(), self.len.tolist()          # the loop's only synchronisation
+            for b in range(S):
+                if keys[b] is not None and dn[b]:
+                    yield keys[b], self.tokens[b, :ln[b]].clone()
+                    keys[b] = None
+            bound = 0
+            for b in range(S):
+                if keys[b] is None and it is not None:
+                    w = next(it, None)
+                    if w is None:
+                        it = None
+                    else:
+                        keys[b] = w[0]
+                        self._refill(b, w[1], w[2], w[3])
+                        ln[b] = 1
+                if keys[b] is not None:
+                    bound = max(bound, ln[b] - 1)
+            if all(k is None for k in keys):
+                return
+            for _ in range(self.check_every):
+                self._run_step(min(bound, self.max_len - 1))
+                bound += 1
+
+
 # DW_ASSIST_TORCH=1 (read when an assisted decode starts): the round stays on the torch ops of `assist_pick_torch` / `assist_accept_torch`
 # on every engine, as on ops without `assist_pick` / `assist_accept` -- the A/B leg of tools/bench_assist.py and the reference leg of
 # tests/test_assist_gpu.py

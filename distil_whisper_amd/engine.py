@@ -1044,6 +1044,44 @@ class WhisperEngine:
         e_pad = st.S[eo:eo + self.ldv * d.d_model].view(self.ldv, d.d_model)
         return ops.gemm(hf, e_pad)
 
+    def decode_token_rows(self, ids, cache, row_t, max_t):
+        """`decode_multi_rows` for ONE new token per row (ids int64 [B, 1]): the step of continuous batching (decoding.SlotDecoder).
+        On the HIP path one call of dw_decode_token_rows -- the token step's launch sequence with the embedding and the self-attention
+        (projection and K/V append inside, where dw_debug_set key 7 has it on) at per-row positions; on ops without the entry
+        `decode_multi_rows`."""
+        assert ids.shape == (cache["B"], 1)
+        if not (self.use_c_decode and hasattr(self.ops, "decode_token_rows")):
+            return self.decode_multi_rows(ids, cache, row_t, max_t)
+        assert row_t.dtype == torch.int32 and row_t.numel() == cache["B"]
+        assert 0 <= max_t and max_t + 1 <= cache["max_len"] and max_t + 1 <= self.dims.max_tgt
+        desc, ws, _, _ = self._decode_desc(cache, 1)
+        ids = ids.contiguous()
+        desc.ids = ids.data_ptr()
+        self.ops.decode_token_rows(desc, row_t, max_t)
+        return ws["logits"]     # (workspace of the cache: valid until the next pass with n = 1)
+
+    def decode_slots_init(self, B, max_len):
+        """A cache as `decode_init` lays it out for B slots that hold no window yet: zeroed self- and cross-attention K/V buffers
+        (cross rows at the pitch of `decode_init`), to be filled slot by slot with `decode_refill`."""
+        ops, d = self.ops, self.dims
+        D = d.d_model
+        return {"B": B, "max_len": max_len, "t": 0,
+                "cross": [ops.zeros((B * d.max_src, 2 * D + self.kv_row_pad), self.lowp)[:, :2 * D] for _ in range(d.dec_layers)],
+                "self": [ops.zeros((B * max_len, 2 * D), self.lowp) for _ in range(d.dec_layers)]}
+
+    def decode_refill(self, cache, slot, enc_rows):
+        """Hand slot `slot` of `cache` to a new window: enc_rows (that window's max_source_positions rows of encoder output) is
+        projected into the slot's rows of every layer's cross-attention K | V buffer, in place (the buffers' addresses are baked
+        into captured graphs) -- the GEMM of `decode_init` over one window's rows, on the caller's stream.  The slot's
+        self-attention rows need no reset: a row decodes from position 0 and reads only what it wrote."""
+        ops, st, d = self.ops, self.st, self.dims
+        D, S = d.d_model, d.max_src
+        assert 0 <= slot < cache["B"] and enc_rows.shape[0] >= S
+        for i in range(d.dec_layers):
+            cv = st.attn_views(f"model.decoder.layers.{i}.encoder_attn")
+            ops.gemm(enc_rows[:S], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=cache["cross"][i][slot * S:(slot + 1) * S],
+                     out_row_pad=self.kv_row_pad)
+
     # ---- backward --------------------------------------------------------------------------------------------------
     def _bias_grad(self, name):
         return self.st.g[name] if self.st.is_trainable(name) else None

@@ -200,6 +200,45 @@ def two_stage_pipeline(owner, ops, dev, batches, encode_fn, decode_fn, overlap, 
         main.wait_stream(s_dec)
 
 
+def encoded_windows(batches, encode_fn, slots, max_src, prompt, max_new):
+    """The `windows` of decoding.SlotDecoder.run from an encoder that runs a batch ahead: whenever fewer encoded windows are waiting
+    than there are slots, the next batch of `batches` is encoded (encode_fn(batch) -> encoder output, max_src rows per window).
+    Keys are (batch index, row in the batch)."""
+    from collections import deque
+    waiting, nxt = deque(), 0
+    while waiting or nxt < len(batches):
+        while len(waiting) < slots and nxt < len(batches):
+            enc = encode_fn(batches[nxt])
+            waiting.extend(((nxt, r), enc[r * max_src:(r + 1) * max_src], prompt, max_new) for r in range(len(batches[nxt])))
+            nxt += 1
+        yield waiting.popleft()
+
+
+def continuous_batches(decoder, batches, encode_fn, max_src, prompt, max_new):
+    """What `two_stage_pipeline` yields -- (batch, ids as a numpy array) in plan order -- decoded by a decoding.SlotDecoder: every
+    window's row is prompt + generated tokens up to its end, padded with the decoder's fill token to the longest row of its batch
+    (the shape the batch path hands on, whose rows carry the fill token behind their end)."""
+    rows = dict(decoder.run(encoded_windows(batches, encode_fn, decoder.S, max_src, prompt, max_new)))
+    for i, batch in enumerate(batches):
+        got = [rows[(i, r)].cpu().numpy() for r in range(len(batch))]
+        ids = np.full((len(batch), max(len(g) for g in got)), decoder.fill, dtype=np.int64)
+        for r, g in enumerate(got):
+            ids[r, :len(g)] = g
+        yield batch, ids
+
+
+def refuse_continuous(who, num_beams=1, assistant=False, seek_loop=False, history=False, overlap=False):
+    """The combinations `continuous=True` does not take, refused when the object is built."""
+    for on, what in ((num_beams > 1, "num_beams > 1"), (assistant, "an assistant_model"), (seek_loop, "timestamp_rules (the seek loop)"),
+                     (history, "repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids")):
+        if on:
+            raise NotImplementedError(f"{who}(continuous=True) with {what} is not implemented on the MI355X path (the slot step "
+                                      "selects plain greedy tokens)")
+    if overlap:
+        raise ValueError(f"{who}(continuous=True, overlap=True): the continuous loop interleaves encoder batches with its own token "
+                         "steps on one stream; choose one of the two")
+
+
 def history_soft(repetition_penalty, no_repeat_ngram_size, sequence_bias=None, bad_words_ids=None, vocab=None, eos_token_id=None):
     """The `soft` argument of decoding.GreedyDecoder for greedy decoding under `repetition_penalty` / `no_repeat_ngram_size` and
     `sequence_bias` / `bad_words_ids` (validated and flattened by decoding.sequence_bias_table for a vocabulary of `vocab` ids);
@@ -229,8 +268,12 @@ class LongFormTranscriber:
                  max_new_tokens=128, prompt_ids=None, eos_token_id=None, first_special_id=None, suppress_tokens=None,
                  begin_suppress_tokens=None, use_graphs=None, rank=0, world=1, return_timestamps=False,
                  no_timestamps_token_id=None, max_initial_timestamp_index=50, special_ids=None, overlap=False,
-                 decode_cus=64, repetition_penalty=None, no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None):
-        """repetition_penalty / no_repeat_ngram_size: GenerationMixin's two rules against repetition loops, applied per window
+                 decode_cus=64, repetition_penalty=None, no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None,
+                 continuous=False, check_every=8):
+        """continuous=True: the windows are decoded by decoding.SlotDecoder -- a window that has ended hands its row of the token
+        loop to the next waiting window instead of idling until the longest window of its batch has ended; same tokens, fewer token
+        steps (`check_every`: steps between two looks at the finished rows).  Needs eos_token_id; not with the history rules below.
+        repetition_penalty / no_repeat_ngram_size: GenerationMixin's two rules against repetition loops, applied per window
         by the selection kernel inside the graph-captured token step (decoding.GreedyDecoder `soft`).
         sequence_bias / bad_words_ids: GenerationMixin's hot-word boosts and forbidden words (`generate` says how they are
         written), applied per window by the same launch; the history they are matched against is the window's own.
@@ -281,11 +324,17 @@ class LongFormTranscriber:
             self.special_ids |= {int(t) for t in self.prompt.tolist() if int(t) >= int(self.first_special)}
             rules = dict(begin_index=len(self.prompt), no_timestamps_token_id=int(no_timestamps_token_id),
                          max_initial_timestamp_index=max_initial_timestamp_index)
+        soft = history_soft(repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, d.vocab, eos_token_id)
+        self.continuous = bool(continuous)
+        if self.continuous:
+            refuse_continuous("LongFormTranscriber", history=soft is not None, overlap=bool(overlap))
+            from .decoding import SlotDecoder
+            self.slot_decoder = SlotDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id,
+                                            suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+                                            timestamp_rules=rules, use_graphs=use_graphs, check_every=check_every)
         self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
                                      suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                     use_graphs=use_graphs, timestamp_rules=rules,
-                                     soft=history_soft(repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids,
-                                                       d.vocab, eos_token_id))
+                                     use_graphs=use_graphs, timestamp_rules=rules, soft=soft)
         self._wave = torch.zeros((self.B, feature_extractor.n_samples), dtype=torch.float32, device=dev)
         # overlap=True (GPU only): the encoder of batch i+1 runs on one HIP stream while the token loop of batch i runs on
         # another.  A batch of 16 windows is ~41 ms of encoder (MFMA-bound, persistent GEMM grids on every CU) followed by ~32 ms
@@ -340,6 +389,10 @@ class LongFormTranscriber:
     def _decoded_batches(self, audios, jobs, prompt):
         """Yields (batch, ids as a numpy array) in order.  overlap: two-stage pipeline over two HIP streams (see __init__)."""
         batches = [jobs[b0:b0 + self.B] for b0 in range(0, len(jobs), self.B)]
+        if self.continuous:
+            yield from continuous_batches(self.slot_decoder, batches, lambda batch: self._encode_batch(audios, batch),
+                                          self.model.dims.max_src, self.prompt, self.max_new)
+            return
         yield from two_stage_pipeline(self, self.model.ops, self.dev, batches, lambda batch: self._encode_batch(audios, batch),
                                       lambda enc: self.decoder.run(enc, prompt, self.max_new), self.overlap, self.decode_cus)
 

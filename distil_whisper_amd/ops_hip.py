@@ -57,6 +57,12 @@ _SIGS = {
     "dw_decode_attn_proj": ([C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                              C.c_float, C.c_void_p], C.c_int),
+    "dw_decode_attn_proj_rows": ([C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float,
+                                  C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
+    "dw_decode_token_rows": ([C.POINTER(DwDecodeStep), C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
+    "dw_slot_step": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int64] +
+                     [C.c_void_p] * 7, C.c_int),
     "dw_logmel": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                    C.c_void_p], C.c_int),
     "dw_gemm_bf16": ([C.POINTER(DwGemm), C.c_void_p], C.c_int),
@@ -424,6 +430,43 @@ class HipOps:
                                                _p(o), o.stride(0), B, H, int(Lk), float(scale), self._stream()), "decode_attn_proj")
         self._t1(e0, "decode_attn_proj", 0.0)
         return o
+
+    def decode_attn_proj_rows(self, x, ln_g, ln_b, w, bias, k, v, B, H, row_t, max_t, *, kv_rows, kv_app, eps=1e-5, scale=0.125,
+                              out=None):
+        """Mode 1 of `decode_attn_proj` with sequence b at position row_t[b] (dw_decode_attn_proj_rows): row_t int32 [B] on the
+        device, max_t the host's bound of its entries.  Thin: the library checks the arguments (include/dwamd.h)."""
+        o = self.empty((B, H * 64), torch.bfloat16) if out is None else out
+        e0 = self._t0()
+        self._chk(self.lib.dw_decode_attn_proj_rows(_p(x), _dt(x), x.stride(0), _p(ln_g), _p(ln_b), float(eps), _p(w), _p(bias), _p(k),
+                                                    _p(v), k.stride(0), int(kv_rows), _p(kv_app), _p(o), o.stride(0), B, H, float(scale),
+                                                    _p(row_t), int(max_t), self._stream()), "decode_attn_proj_rows")
+        self._t1(e0, "decode_attn_proj_rows", 0.0)
+        return o
+
+    def decode_token_rows(self, desc, row_t, max_t):
+        """The token step with row b at position row_t[b] (dw_decode_token_rows; desc.n_new == 1): `decode_pass_rows` keeping the
+        self-attention with its projection inside."""
+        assert row_t.dtype == torch.int32 and row_t.is_contiguous() and row_t.numel() >= desc.batch and row_t.device == self.device
+        e0 = self._t0()
+        self._chk(self.lib.dw_decode_token_rows(C.byref(desc), _p(row_t), int(max_t), self._stream()), "decode_token_rows")
+        self._t1(e0, "decode_token_rows", 0.0)
+
+    def slot_step(self, logits, V, tokens, length, plen, budget, done, row_t, cur, *, suppress=None, begin_suppress=None, ts_begin=-1,
+                  max_initial=-1, eos=-1, min_new=0):
+        """The token selection of continuous batching for every slot in one launch (dw_slot_step, csrc/slots.hip): logits bf16
+        [S, ld]; tokens int64 [S, max_len]; length / plen / budget / row_t int32 [S]; done bool [S]; cur int64 [S, 1]; all
+        updated in place on the device."""
+        S = tokens.shape[0]
+        assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= S
+        assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() >= S
+        for m in (suppress, begin_suppress):
+            assert m is None or (m.dtype == torch.uint8 and m.numel() >= V and m.is_contiguous())
+        for a in (length, plen, budget, row_t):
+            assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() >= S
+        assert done.dtype == torch.bool and done.is_contiguous() and done.numel() >= S
+        self._chk(self.lib.dw_slot_step(_p(logits), S, int(V), logits.stride(0), _p(suppress), _p(begin_suppress), int(ts_begin),
+                                        int(max_initial), int(eos), int(min_new), _p(tokens), tokens.stride(0), _p(length), _p(plen),
+                                        _p(budget), _p(done), _p(row_t), _p(cur), self._stream()), "slot_step")
 
     def layernorm_fwd(self, x, gamma, beta, eps=1e-5, save_stats=True, out=None):
         """x, out: 2-D with unit column stride; their row pitches may exceed the row length (padded activation buffers)."""

@@ -46,8 +46,9 @@ class PseudoLabeller:
     def __init__(self, model, feature_extractor, batch_size=16, max_new_tokens=255, prompt_ids=None, eos_token_id=None,
                  timestamp_rules=None, use_graphs=None, rank=0, world=1, suppress_tokens=None,
                  begin_suppress_tokens=None, num_beams=1, overlap=False, decode_cus=64, repetition_penalty=None,
-                 no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None, assistant_model=None, num_assistant_tokens=5):
-        from .longform import history_soft
+                 no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None, assistant_model=None, num_assistant_tokens=5,
+                 continuous=False, check_every=8):
+        from .longform import history_soft, refuse_continuous
         self.model, self.fe = model, feature_extractor
         self.B, self.max_new = int(batch_size), int(max_new_tokens)
         self.rank, self.world = rank, world
@@ -89,6 +90,16 @@ class PseudoLabeller:
             timestamp_rules = dict(timestamp_rules, begin_index=len(self.prompt))
         self._ts_rules = timestamp_rules
         self.eos = eos_token_id
+        # continuous=True: the plain greedy path on decoding.SlotDecoder -- a pack whose labels have ended hands its row of the token
+        # loop to the next waiting pack; the encoder runs a batch ahead of the slots (longform.encoded_windows).  Same labels.
+        self.continuous = bool(continuous)
+        if self.continuous:
+            refuse_continuous("PseudoLabeller", self.num_beams, assistant_model is not None, timestamp_rules is not None,
+                              soft is not None, bool(overlap))
+            from .decoding import SlotDecoder
+            self.slot_decoder = SlotDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id,
+                                            suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+                                            use_graphs=use_graphs, check_every=check_every)
         self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
                                      suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
                                      use_graphs=use_graphs, timestamp_rules=timestamp_rules, soft=soft)
@@ -139,8 +150,12 @@ class PseudoLabeller:
             decode = lambda encs: assisted_greedy_decode(model.engine, am.engine, encs[0], encs[1], prompt, self.max_new,
                                                          self.num_assistant_tokens, **self._assist_kw)[0]
         if plain:
-            from .longform import two_stage_pipeline
-            for batch, ids in two_stage_pipeline(self, model.ops, self.dev, batches, encode, decode, self.overlap, self.decode_cus):
+            from .longform import continuous_batches, two_stage_pipeline
+            if self.continuous:
+                decoded = continuous_batches(self.slot_decoder, batches, encode, model.dims.max_src, self.prompt, self.max_new)
+            else:
+                decoded = two_stage_pipeline(self, model.ops, self.dev, batches, encode, decode, self.overlap, self.decode_cus)
+            for batch, ids in decoded:
                 for r, pi in enumerate(batch):
                     row = ids[r, self.prompt.numel():].tolist()
                     if self.eos is not None and self.eos in row:

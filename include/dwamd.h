@@ -517,6 +517,42 @@ int dw_decode_step_rows(const DwDecodeStep* d, const int32_t* row_t, int32_t max
 int dw_decode_attn_proj(int mode, const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps,
                         const void* w, const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows,
                         void* kv_app, void* o, int64_t ldo, int B, int H, int Lk, float scale, void* stream);
+/* dw_decode_attn_proj_rows: mode 1 of dw_decode_attn_proj with sequence b at its own position: row_t int32 [B] in DEVICE memory
+ * (the host never reads it; the kernel reads an entry outside [0, max_t] as the nearer end of that range), max_t the host's bound.
+ * Sequence b writes k_new | v_new to row row_t[b] of its rows of kv_app and its softmax runs over row_t[b] + 1 keys; the workgroup
+ * of (b, h) performs the arithmetic of the uniform kernel at Lk = row_t[b] + 1 in the same order, so o[b] and the appended row
+ * are what dw_decode_attn_proj(mode 1, Lk = row_t[b] + 1) writes for that sequence, bit for bit.  LDS is sized by max_t + 1.
+ * The refusals of dw_decode_attn_proj with Lk = max_t + 1, in front of the launch, and: DW_EINVAL for a null or misaligned row_t,
+ * max_t < 0, max_t + 1 > kv_rows; DW_EUNSUP for max_t + 1 > 8192. */
+int dw_decode_attn_proj_rows(const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps, const void* w,
+                             const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows, void* kv_app, void* o,
+                             int64_t ldo, int B, int H, float scale, const int32_t* row_t, int32_t max_t, void* stream);
+/* dw_decode_token_rows: the token step (n_new == 1, else DW_EINVAL) with row b at position row_t[b] (row_t / max_t as for
+ * dw_decode_step_rows): the launch sequence of dw_decode_step at n_new == 1 with two launches swapped -- the embedding takes the
+ * position row per sequence, the self-attention with its projection and K/V append inside is dw_decode_attn_proj_rows.  With equal
+ * positions the logits and caches are those of dw_decode_step, bit for bit.  Where D = 64 * heads has no such kernel, max_t + 1 >
+ * 8192 or dw_debug_set key 7 has bit 2 set (the default: see there), the self-attention is that of dw_decode_step_rows (QKV GEMM,
+ * append, attention over per-row key counts) and the pass is dw_decode_step_rows' own.  The step of continuous batching
+ * (dw_slot_step below writes row_t and ids).  Nothing is allocated, nothing synchronises. */
+int dw_decode_token_rows(const DwDecodeStep* d, const int32_t* row_t, int32_t max_t, void* stream);
+/* dw_slot_step: the token selection of continuous batching (csrc/slots.hip), one 1024-thread workgroup per slot b < S.  Device
+ * state per slot: tokens int64 [S][tok_ld], len (tokens held = the position this step fills), plen (prompt length = begin_index
+ * of the rules), budget (plen + max_new_tokens, <= tok_ld), done, and the feed of the next pass row_t / cur (int64 [S]).
+ * logits bf16 [S][ld]: row b is the output of the pass that fed cur[b] at position row_t[b].  With n = len[b]:
+ *   done[b]                 the row is left alone; row_t[b] = 0, cur[b] = tokens[b][0] (parked at position 0)
+ *   n < plen[b]             nxt = tokens[b][n] (teacher forcing)
+ *   otherwise               nxt = the best allowed column of the row under suppress / begin_suppress (first = n == plen[b]),
+ *                           min-new-tokens (EOS excluded while n - plen[b] < min_new) and the timestamp rules (ts_begin =
+ *                           no_timestamps_token_id + 1, < 0: off; max_initial < 0: none) with the history tokens[b][0 .. n)
+ *   then tokens[b][n] = nxt, len[b] = n + 1; a generated nxt that is `eos` or fills the budget (n + 1 >= budget[b]) sets done[b]
+ *   and parks the slot, else row_t[b] = n, cur[b] = nxt.
+ * A slot whose state no refill leaves behind (len < 1, len >= tok_ld, plen < 1) is set done and parked.  DW_EINVAL: a null or
+ * misaligned pointer, S outside [1, 65535], tok_ld < 2, V < 1, ld < V, ld not a multiple of 4, logits not 8-byte aligned, the
+ * timestamp rules without eos.  One launch; no argument depends on a position: with dw_decode_token_rows it replays from one HIP
+ * graph. */
+int dw_slot_step(const void* logits, int S, int V, int64_t ld, const uint8_t* suppress, const uint8_t* begin_suppress, int ts_begin,
+                 int max_initial, int eos, int min_new, int64_t* tokens, int64_t tok_ld, int32_t* len, const int32_t* plen,
+                 const int32_t* budget, uint8_t* done, int32_t* row_t, int64_t* cur, void* stream);
 
 /* ---- token-level timestamps (TF:generation_whisper.py:241-381 `_extract_token_timestamps`, :43-61 `_median_filter`, :64-115
  * `_dynamic_time_warping`; reached from `generate(return_token_timestamps=True)`, TF:1146-1157).  The reference collects every
