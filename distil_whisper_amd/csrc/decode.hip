@@ -1034,11 +1034,23 @@ static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void*
     if (ldx < 2L * D || (ldx & 7)) return DW_EINVAL;
     const int ldk = (t + n + 3) & ~3;                                     // rows pass: pitch of a query's scores in LDS
     const size_t rows_smem = attn_rows_smem(n, ldk);
+    // FP8 cross-attention K/V (include/dwamd.h): only the token step's kernel reads them -- refused before anything is launched
+    const bool kv8 = d->cross_kv_fmt == 1;
+    if (d->cross_kv_fmt != 0 && !kv8) return DW_EINVAL;
+    if (kv8) {
+        if (n != 1 || (row_t && !token_rows) || !decode_proj_dim_ok(D) || (g_decode_fuse_off & 8) || d->src_len > 8192 || B > 65535)
+            return DW_EUNSUP;
+        for (int l = 0; l < d->n_layers; ++l) {
+            const DwDecoderLayer& L = d->layers[l];
+            if (!L.cross_k8 || !L.cross_v8 || !L.cross_scale || !L.bq || !L.ln2_g || !L.ln2_b) return DW_EINVAL;
+            if ((((uintptr_t)L.cross_k8 | (uintptr_t)L.cross_v8) & 15) || ((uintptr_t)L.cross_scale & 3)) return DW_EINVAL;
+        }
+    }
     if (row_t) {                                                          // (refused before anything is launched)
         if (n > AR_MAXQ || B > 65535 || rows_smem > 65536) return DW_EUNSUP;
         for (int l = 0; l < d->n_layers; ++l) {
             const DwDecoderLayer& L = d->layers[l];
-            if (!L.wqkv || !L.wo || !L.wq || !L.wo2 || !L.w1 || !L.w2 || !L.self_kv || !L.cross_kv) return DW_EINVAL;
+            if (!L.wqkv || !L.wo || !L.wq || !L.wo2 || !L.w1 || !L.w2 || !L.self_kv || (!kv8 && !L.cross_kv)) return DW_EINVAL;
         }
     }
     const size_t es = d->stream_dtype == DW_F32 ? 4 : 2;
@@ -1090,7 +1102,7 @@ static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void*
     };
     for (int l = 0; l < d->n_layers; ++l) {
         const DwDecoderLayer& L = d->layers[l];
-        if (!L.wqkv || !L.wo || !L.wq || !L.wo2 || !L.w1 || !L.w2 || !L.self_kv || !L.cross_kv) return DW_EINVAL;
+        if (!L.wqkv || !L.wo || !L.wq || !L.wo2 || !L.w1 || !L.w2 || !L.self_kv || (!kv8 && !L.cross_kv)) return DW_EINVAL;
         // ---- self-attention over the cached prefix ----
         if (proj_self && L.bqkv && L.ln1_g && L.ln1_b) {
             const bf16* kc0 = (const bf16*)L.self_kv;
@@ -1130,7 +1142,10 @@ static int decode_pass(const DwDecodeStep* d, const int32_t* row_t, int t, void*
         if ((rc = gemm(d->o, D, L.wo, L.bo, D, D, d->x, D, d->stream_dtype, 0, d->x, nullptr, nullptr, nullptr)) != DW_OK)
             return rc;
         // ---- cross-attention over the static encoder K/V ----
-        if (proj_cross && L.bq && L.ln2_g && L.ln2_b) {
+        if (kv8) {
+            if ((rc = dw_decode_attn_proj_kv8(d->x, d->stream_dtype, D, L.ln2_g, L.ln2_b, 1e-5f, L.wq, L.bq, L.cross_k8, L.cross_v8,
+                                              L.cross_scale, d->src_len, d->o, D, B, H, d->src_len, 0.125f, stream)) != DW_OK) return rc;
+        } else if (proj_cross && L.bq && L.ln2_g && L.ln2_b) {
             const bf16* kx0 = (const bf16*)L.cross_kv;
             if ((rc = dw_decode_attn_proj(0, d->x, d->stream_dtype, D, L.ln2_g, L.ln2_b, 1e-5f, L.wq, L.bq, kx0, kx0 + D, ldx, d->src_len,
                                           nullptr, d->o, D, B, H, d->src_len, 0.125f, stream)) != DW_OK) return rc;

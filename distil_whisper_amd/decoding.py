@@ -14,6 +14,8 @@ import os
 
 import torch
 
+from . import kv_quant
+
 # DW_SAMPLE_TORCH=1 (read when a decoder is built): sampling stays on the torch ops of `_select_soft` on every engine, as on ops
 # without `sample_select` -- the A/B leg of tools/bench_sample_select.py and the reference leg of tests/test_sample_select_gpu.py
 SAMPLE_TORCH_ENV = "DW_SAMPLE_TORCH"
@@ -286,9 +288,14 @@ def processed_scores(scores, hist, n, *, begin_index, eos=None, no_eos=False, fi
 
 class GreedyDecoder:
     def __init__(self, engine, batch, max_len, eos_token_id=None, suppress_tokens=None, begin_suppress_tokens=None,
-                 use_graphs=None, check_every=16, timestamp_rules=None, pad_token_id=None, soft=None):
+                 use_graphs=None, check_every=16, timestamp_rules=None, pad_token_id=None, soft=None, cross_kv_dtype=None):
         self.eng, self.B, self.max_len = engine, int(batch), int(max_len)
         d = engine.dims
+        # "fp8": the cross-attention K/V of the cache as e4m3fn codes with column scales (engine.decode_init; include/dwamd.h) --
+        # opt-in, it changes the numerics of the token step; None / "bf16": the cache as it always was
+        self.cross_kv_dtype = kv_quant.normalize_dtype(cross_kv_dtype)
+        if self.cross_kv_dtype is not None:
+            kv_quant.check_width(d.d_model)
         if self.max_len > d.max_tgt:
             raise ValueError(f"max_len = {max_len} exceeds max_target_positions = {d.max_tgt}")
         dev = engine.ops.device
@@ -426,7 +433,7 @@ class GreedyDecoder:
         total = P + int(max_new_tokens)
         if total > self.max_len:
             raise ValueError(f"prompt + max_new_tokens = {total} exceeds the decoder's max_len = {self.max_len}")
-        self.cache = self.eng.decode_init(enc_out, B, self.max_len, cache=self.cache)
+        self.cache = self.eng.decode_init(enc_out, B, self.max_len, cache=self.cache, cross_kv_dtype=self.cross_kv_dtype)
         self.tokens.zero_()
         self.tokens[:, :P].copy_(prompt_ids)
         self.done.zero_()
@@ -496,9 +503,12 @@ class SlotDecoder:
     BUCKET = 64
 
     def __init__(self, engine, slots, max_len, eos_token_id, suppress_tokens=None, begin_suppress_tokens=None, timestamp_rules=None,
-                 min_new_tokens=0, pad_token_id=None, use_graphs=None, check_every=8):
+                 min_new_tokens=0, pad_token_id=None, use_graphs=None, check_every=8, cross_kv_dtype=None):
         self.eng, self.S, self.max_len = engine, int(slots), int(max_len)
         d = engine.dims
+        self.cross_kv_dtype = kv_quant.normalize_dtype(cross_kv_dtype)      # "fp8": see GreedyDecoder
+        if self.cross_kv_dtype is not None:
+            kv_quant.check_width(d.d_model)
         if self.S < 1 or int(check_every) < 1:
             raise ValueError("SlotDecoder needs at least one slot and check_every >= 1")
         if self.max_len > d.max_tgt:
@@ -580,7 +590,7 @@ class SlotDecoder:
     def run(self, windows):
         S = self.S
         if self.cache is None:
-            self.cache = self.eng.decode_slots_init(S, self.max_len)
+            self.cache = self.eng.decode_slots_init(S, self.max_len, cross_kv_dtype=self.cross_kv_dtype)
         self.done.fill_(True)                         # every slot empty: parked until a window takes it
         keys = [None] * S
         it = iter(windows)

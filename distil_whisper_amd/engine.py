@@ -17,6 +17,8 @@ import ctypes as C
 
 import torch
 
+from . import kv_quant
+
 
 @dataclass
 class WhisperDims:
@@ -818,23 +820,57 @@ class WhisperEngine:
         return probs
 
     # ---- incremental decoding with a KV cache (TF:modeling_whisper.py:312-335, EncoderDecoderCache) -----------------
-    def decode_init(self, enc_out, B, max_len, cache=None):
+    def decode_init(self, enc_out, B, max_len, cache=None, cross_kv_dtype=None):
         """Per decoder layer: the static cross-attention K/V projected once from the encoder output, and an empty
         self-attention K/V cache laid out [B][max_len][2D] that the attention kernel reads in place (batch pitch =
         max_len rows).  Passing a `cache` made by an earlier call with the same (B, max_len) refills its buffers in
-        place (their addresses are baked into captured HIP graphs, see decoding.GreedyDecoder)."""
+        place (their addresses are baked into captured HIP graphs, see decoding.GreedyDecoder).
+        cross_kv_dtype="fp8" (None / "bf16": the cache above): every layer's projection GEMM writes into ONE bf16 staging buffer,
+        and the quantiser fills the layer's FP8 codes and column scales from it (include/dwamd.h, "FP8 cross-attention K/V") --
+        half the cross bytes plus one layer of staging.  Only the token step reads such a cache (`decode_step`,
+        `decode_token_rows`); a refill needs no dtype (the cache knows its own; one that is given must agree)."""
         ops, st, d = self.ops, self.st, self.dims
         D, Re = d.d_model, B * d.max_src
+        fp8 = kv_quant.normalize_dtype(cross_kv_dtype) == "fp8" if cache is None else "cross8" in cache
+        assert cross_kv_dtype is None or fp8 == (kv_quant.normalize_dtype(cross_kv_dtype) == "fp8"), "the cache has the other format"
         if cache is None:
             cache = {"B": B, "max_len": max_len, "t": 0, "cross": [None] * d.dec_layers,
                      "self": [ops.zeros((B * max_len, 2 * D), self.lowp) for _ in range(d.dec_layers)]}
+            if fp8:
+                cache.update(self._cross8_alloc(B, B))
         assert cache["B"] == B and cache["max_len"] == max_len
         cache["t"] = 0
         for i in range(d.dec_layers):
             cv = st.attn_views(f"model.decoder.layers.{i}.encoder_attn")
-            cache["cross"][i] = ops.gemm(enc_out[:Re], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=cache["cross"][i],
-                                         out_row_pad=self.kv_row_pad)
+            if fp8:
+                ops.gemm(enc_out[:Re], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=cache["cross_stage"])
+                self._cross8_quant(cache, i, 0, B)
+            else:
+                cache["cross"][i] = ops.gemm(enc_out[:Re], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=cache["cross"][i],
+                                             out_row_pad=self.kv_row_pad)
         return cache
+
+    def _cross8_alloc(self, B, stage_seqs):
+        """The FP8 cross-attention buffers of a cache of B sequences: per layer (codes of K, codes of V uint8 [B, H, src, 64],
+        scales f32 [B, 2, D]) and the bf16 staging rows of `stage_seqs` sequences that every layer's projection passes through."""
+        ops, d = self.ops, self.dims
+        kv_quant.check_width(d.d_model)
+        D, H, S = d.d_model, d.heads, d.max_src
+
+        def layer():
+            sc = ops.zeros((B, 2, D), torch.float32)
+            sc.fill_(1.0)                                  # (an all-zero column has scale 1: a slot no window has filled yet)
+            return (ops.zeros((B, H, S, 64), torch.uint8), ops.zeros((B, H, S, 64), torch.uint8), sc)
+        return {"cross8": [layer() for _ in range(d.dec_layers)], "cross_stage": ops.zeros((stage_seqs * S, 2 * D), self.lowp)}
+
+    def _cross8_quant(self, cache, layer, seq0, n_seq):
+        """Codes and scales of sequences [seq0, seq0 + n_seq) of `layer` from the first n_seq * src rows of the staging buffer."""
+        ops, d = self.ops, self.dims
+        k8, v8, sc = cache["cross8"][layer]
+        if hasattr(ops, "cross_kv_quant"):
+            ops.cross_kv_quant(cache["cross_stage"], k8, v8, sc, seq0, n_seq, d.max_src, d.heads)
+        else:
+            kv_quant.quantize_into(cache["cross_stage"], k8, v8, sc, seq0, n_seq, d.max_src, d.heads)
 
     # ---- single-call decoder pass (C entry dw_decode_step) ---------------------------------------------------------
     # the FFN's saved by-product is gelu'(z) in fp16 (the backward epilogue multiplies) instead of z in bf16 (it
@@ -880,15 +916,22 @@ class WhisperEngine:
             L.ln3_g, L.ln3_b = st.p[f"{p}.final_layer_norm.weight"].data_ptr(), st.p[f"{p}.final_layer_norm.bias"].data_ptr()
             L.w1, L.b1 = st.s[f"{p}.fc1.weight"].data_ptr(), st.p[f"{p}.fc1.bias"].data_ptr()
             L.w2, L.b2 = st.s[f"{p}.fc2.weight"].data_ptr(), st.p[f"{p}.fc2.bias"].data_ptr()
-            L.self_kv, L.cross_kv = cache["self"][i].data_ptr(), cache["cross"][i].data_ptr()
+            L.self_kv = cache["self"][i].data_ptr()
+            if "cross8" in cache:
+                L.cross_k8, L.cross_v8, L.cross_scale = (b.data_ptr() for b in cache["cross8"][i])
+            else:
+                L.cross_kv = cache["cross"][i].data_ptr()
             keep += [av, cv]
         eo = st.entries["model.decoder.embed_tokens.weight"][0]
         desc = DwDecodeStep()
         desc.batch, desc.n_new, desc.d_model, desc.heads, desc.ffn, desc.n_layers = B, n, D, d.heads, F, d.dec_layers
         desc.src_len, desc.max_len, desc.vocab, desc.ldv = d.max_src, cache["max_len"], d.vocab, self.ldv
         desc.stream_dtype = DW_F32 if f32 else DW_BF16
-        desc.cross_kv_ld = cache["cross"][0].stride(0)
-        assert all(c.stride(0) == desc.cross_kv_ld for c in cache["cross"])
+        if "cross8" in cache:
+            desc.cross_kv_fmt = 1
+        else:
+            desc.cross_kv_ld = cache["cross"][0].stride(0)
+            assert all(c.stride(0) == desc.cross_kv_ld for c in cache["cross"])
         desc.tok_emb = tab["model.decoder.embed_tokens.weight"].data_ptr()
         desc.pos_emb = tab["model.decoder.embed_positions.weight"].data_ptr()
         desc.lnf_g, desc.lnf_b = st.p["model.decoder.layer_norm.weight"].data_ptr(), st.p["model.decoder.layer_norm.bias"].data_ptr()
@@ -950,8 +993,11 @@ class WhisperEngine:
             ln2 = (st.p[f"{p}.encoder_attn_layer_norm.weight"], st.p[f"{p}.encoder_attn_layer_norm.bias"], 1e-5)
             h = x if fuse_ln else ops.layernorm_fwd(x, *ln2, save_stats=False)[0]
             q = ops.gemm(h, cv["wqkv"][:D], bias=cv["bqkv"][:D], ln=ln2[:2] if fuse_ln else None)
-            kv = cache["cross"][i]
-            o, _ = ops.attn_fwd(q, kv[:, :D], kv[:, D:], B, H, n, Lk, False, 0.125)
+            if "cross8" in cache:               # FP8 cross K/V: the torch statement of the format (kv_quant; the kernel is dw_decode_step's)
+                o = kv_quant.attention(q, *cache["cross8"][i], 0.125, out_dtype=self.lowp)
+            else:
+                kv = cache["cross"][i]
+                o, _ = ops.attn_fwd(q, kv[:, :D], kv[:, D:], B, H, n, Lk, False, 0.125)
             x = ops.gemm(o, cv["wo"], bias=cv["bo"], residual=x, round_res=True, out_dtype=self.stream)
             ln3 = (st.p[f"{p}.final_layer_norm.weight"], st.p[f"{p}.final_layer_norm.bias"], 1e-5)
             h = x if fuse_ln else ops.layernorm_fwd(x, *ln3, save_stats=False)[0]
@@ -992,6 +1038,8 @@ class WhisperEngine:
         prompt prefill.  cache["t"] advances by n; callers roll it back to drop rejected positions.  The returned logits
         alias the cache's workspace for this n on the HIP path (see decode_step)."""
         ops, st, d = self.ops, self.st, self.dims
+        if "cross8" in cache:
+            raise NotImplementedError("an FP8 cross-attention cache serves the token step only (decode_step, decode_token_rows)")
         B, t, ML = cache["B"], cache["t"], cache["max_len"]
         n = ids.shape[1]
         D, H, Lk = d.d_model, d.heads, d.max_src
@@ -1019,12 +1067,17 @@ class WhisperEngine:
         nor moved: the caller owns the positions (speculative decoding with per-row acceptance, decoding.assisted_greedy_decode).
         On the HIP path this is ONE call of dw_decode_step_rows, which never brings row_t to the host; on other ops (oracle.ref_ops,
         CPU) the per-kernel form: position rows gathered by indexing, K/V written by indexing, one `ops.attn_fwd` per row."""
+        if "cross8" in cache:
+            raise NotImplementedError("an FP8 cross-attention cache serves the token step only (decode_step, decode_token_rows)")
+        return self._decode_multi_rows(ids, cache, row_t, max_t)
+
+    def _decode_multi_rows(self, ids, cache, row_t, max_t):
         ops, st, d = self.ops, self.st, self.dims
         B, ML = cache["B"], cache["max_len"]
         n = ids.shape[1]
         assert ids.shape[0] == B and row_t.dtype == torch.int32 and row_t.numel() == B
         assert 0 <= max_t and max_t + n <= ML and max_t + n <= d.max_tgt
-        if self.use_c_decode and hasattr(ops, "decode_pass_rows"):
+        if self.use_c_decode and hasattr(ops, "decode_pass_rows") and "cross8" not in cache:
             desc, ws, _, _ = self._decode_desc(cache, n)
             ids = ids.contiguous()
             desc.ids = ids.data_ptr()
@@ -1051,7 +1104,7 @@ class WhisperEngine:
         `decode_multi_rows`."""
         assert ids.shape == (cache["B"], 1)
         if not (self.use_c_decode and hasattr(self.ops, "decode_token_rows")):
-            return self.decode_multi_rows(ids, cache, row_t, max_t)
+            return self._decode_multi_rows(ids, cache, row_t, max_t)
         assert row_t.dtype == torch.int32 and row_t.numel() == cache["B"]
         assert 0 <= max_t and max_t + 1 <= cache["max_len"] and max_t + 1 <= self.dims.max_tgt
         desc, ws, _, _ = self._decode_desc(cache, 1)
@@ -1060,27 +1113,38 @@ class WhisperEngine:
         self.ops.decode_token_rows(desc, row_t, max_t)
         return ws["logits"]     # (workspace of the cache: valid until the next pass with n = 1)
 
-    def decode_slots_init(self, B, max_len):
+    def decode_slots_init(self, B, max_len, cross_kv_dtype=None):
         """A cache as `decode_init` lays it out for B slots that hold no window yet: zeroed self- and cross-attention K/V buffers
-        (cross rows at the pitch of `decode_init`), to be filled slot by slot with `decode_refill`."""
+        (cross rows at the pitch of `decode_init`), to be filled slot by slot with `decode_refill`.  cross_kv_dtype="fp8": FP8
+        codes and scales per layer as in `decode_init`, and one window's rows of bf16 staging."""
         ops, d = self.ops, self.dims
         D = d.d_model
-        return {"B": B, "max_len": max_len, "t": 0,
-                "cross": [ops.zeros((B * d.max_src, 2 * D + self.kv_row_pad), self.lowp)[:, :2 * D] for _ in range(d.dec_layers)],
-                "self": [ops.zeros((B * max_len, 2 * D), self.lowp) for _ in range(d.dec_layers)]}
+        cache = {"B": B, "max_len": max_len, "t": 0, "cross": [None] * d.dec_layers,
+                 "self": [ops.zeros((B * max_len, 2 * D), self.lowp) for _ in range(d.dec_layers)]}
+        if kv_quant.normalize_dtype(cross_kv_dtype) == "fp8":
+            cache.update(self._cross8_alloc(B, 1))
+        else:
+            cache["cross"] = [ops.zeros((B * d.max_src, 2 * D + self.kv_row_pad), self.lowp)[:, :2 * D] for _ in range(d.dec_layers)]
+        return cache
 
     def decode_refill(self, cache, slot, enc_rows):
         """Hand slot `slot` of `cache` to a new window: enc_rows (that window's max_source_positions rows of encoder output) is
         projected into the slot's rows of every layer's cross-attention K | V buffer, in place (the buffers' addresses are baked
         into captured graphs) -- the GEMM of `decode_init` over one window's rows, on the caller's stream.  The slot's
-        self-attention rows need no reset: a row decodes from position 0 and reads only what it wrote."""
+        self-attention rows need no reset: a row decodes from position 0 and reads only what it wrote.
+        An FP8 cache quantises the slot's sequence alone: the scales are per sequence, so the other slots' codes and scales are
+        neither read nor written and the slot holds what `decode_init` would have given that window."""
         ops, st, d = self.ops, self.st, self.dims
         D, S = d.d_model, d.max_src
         assert 0 <= slot < cache["B"] and enc_rows.shape[0] >= S
         for i in range(d.dec_layers):
             cv = st.attn_views(f"model.decoder.layers.{i}.encoder_attn")
-            ops.gemm(enc_rows[:S], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=cache["cross"][i][slot * S:(slot + 1) * S],
-                     out_row_pad=self.kv_row_pad)
+            if "cross8" in cache:
+                ops.gemm(enc_rows[:S], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=cache["cross_stage"][:S])
+                self._cross8_quant(cache, i, slot, 1)
+            else:
+                ops.gemm(enc_rows[:S], cv["wqkv"][D:], bias=cv["bqkv"][D:], out=cache["cross"][i][slot * S:(slot + 1) * S],
+                         out_row_pad=self.kv_row_pad)
 
     # ---- backward --------------------------------------------------------------------------------------------------
     def _bias_grad(self, name):

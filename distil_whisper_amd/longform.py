@@ -269,8 +269,10 @@ class LongFormTranscriber:
                  begin_suppress_tokens=None, use_graphs=None, rank=0, world=1, return_timestamps=False,
                  no_timestamps_token_id=None, max_initial_timestamp_index=50, special_ids=None, overlap=False,
                  decode_cus=64, repetition_penalty=None, no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None,
-                 continuous=False, check_every=8):
-        """continuous=True: the windows are decoded by decoding.SlotDecoder -- a window that has ended hands its row of the token
+                 continuous=False, check_every=8, cross_kv_dtype=None):
+        """cross_kv_dtype="fp8": the token loops keep the cross-attention K/V as FP8 codes with column scales (include/dwamd.h) --
+        half the bytes the token step streams; opt-in: the tokens may differ from the bf16 cache's where two logits are close.
+        continuous=True: the windows are decoded by decoding.SlotDecoder -- a window that has ended hands its row of the token
         loop to the next waiting window instead of idling until the longest window of its batch has ended; same tokens, fewer token
         steps (`check_every`: steps between two looks at the finished rows).  Needs eos_token_id; not with the history rules below.
         repetition_penalty / no_repeat_ngram_size: GenerationMixin's two rules against repetition loops, applied per window
@@ -331,10 +333,11 @@ class LongFormTranscriber:
             from .decoding import SlotDecoder
             self.slot_decoder = SlotDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id,
                                             suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                            timestamp_rules=rules, use_graphs=use_graphs, check_every=check_every)
+                                            timestamp_rules=rules, use_graphs=use_graphs, check_every=check_every,
+                                            cross_kv_dtype=cross_kv_dtype)
         self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
                                      suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                     use_graphs=use_graphs, timestamp_rules=rules, soft=soft)
+                                     use_graphs=use_graphs, timestamp_rules=rules, soft=soft, cross_kv_dtype=cross_kv_dtype)
         self._wave = torch.zeros((self.B, feature_extractor.n_samples), dtype=torch.float32, device=dev)
         # overlap=True (GPU only): the encoder of batch i+1 runs on one HIP stream while the token loop of batch i runs on
         # another.  A batch of 16 windows is ~41 ms of encoder (MFMA-bound, persistent GEMM grids on every CU) followed by ~32 ms

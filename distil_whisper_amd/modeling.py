@@ -807,7 +807,7 @@ class WhisperForConditionalGeneration(nn.Module):
                  temperature=None, compression_ratio_threshold=None, logprob_threshold=None, no_speech_threshold=None,
                  num_segment_frames=None, attention_mask=None, time_precision=0.02, time_precision_features=0.01,
                  return_token_timestamps=None, return_segments=False, return_dict_in_generate=None,
-                 force_unique_generate_call=None, monitor_progress=None, *, use_graphs=None, **kwargs):
+                 force_unique_generate_call=None, monitor_progress=None, *, use_graphs=None, cross_kv_dtype=None, **kwargs):
         """`WhisperGenerationMixin.generate` (TF:generation_whisper.py:383-968) on the MI355X engine, with the argument
         list of the reference (run_distillation.py:1524-1528, run_eval.py:690-739, 806-844): greedy search over one
         30 s window per row with language / task / timestamp / prompt_ids prefixes, the suppress / begin-suppress /
@@ -851,6 +851,13 @@ class WhisperForConditionalGeneration(nn.Module):
         finished sequences and three kernels (alignment.extract_token_timestamps) -- the result is a dict {"sequences",
         "token_timestamps"[, "segments"]} as in the reference (TF:941-968); `attention_mask` gives the valid frames per row;
         `alignment_heads=[[layer, head], ...]` may be passed like any other generation-config field.
+        `cross_kv_dtype="fp8"` (None / "bf16": today's cache): the KV-cache decoder keeps the cross-attention K/V as e4m3fn codes
+        with one scale per column (include/dwamd.h; README "FP8 cross-attention K/V") -- half the bytes the token step streams.
+        Opt-in: it changes the numerics of the token step, so a token may differ where two logits are close.  Single-window greedy
+        or sampled decoding on the KV cache, with or without graphs, with the timestamp rules under `force_unique_generate_call`
+        and the repetition / bias options.  The seek loop, `num_beams > 1`, an `assistant_model`, `output_scores` /
+        `output_logits` and `return_token_timestamps` RAISE NotImplementedError before the encoder runs; `use_cache=False`, any
+        other value and a model width without the kernel are a ValueError.
         Returns what the reference returns: the generated tokens only (decoder prompt and EOS stripped, right-padded
         with pad_token_id), or with `return_dict_in_generate=True` / `force_unique_generate_call=True` the full
         sequences (prompt + generated, as GenerationMixin emits them)."""
@@ -971,6 +978,21 @@ class WhisperForConditionalGeneration(nn.Module):
                 nf = None
             token_ts = dict(alignment_heads=[list(x) for x in gc.alignment_heads], num_frames=nf,
                             time_precision=time_precision)
+        # ---- FP8 cross-attention K/V: only the token step of decoding.GreedyDecoder reads them; refused before the encoder runs
+        from . import kv_quant
+        cross_kv_dtype = kv_quant.normalize_dtype(cross_kv_dtype)
+        if cross_kv_dtype is not None:
+            kv_quant.check_width(d.d_model)
+            if kwargs.get("use_cache", True) is False:
+                raise ValueError('cross_kv_dtype="fp8" is a format of the KV cache (not with use_cache=False)')
+            for on, combo in ((num_beams > 1, "beam search (num_beams > 1)"),
+                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
+                              (want_scores or want_logits, "output_scores / output_logits"),
+                              (bool(return_token_timestamps), "return_token_timestamps"),
+                              (uses_fallback, "the temperature fallback / condition_on_prev_tokens (the seek loop)")):
+                if on:
+                    raise NotImplementedError(f'cross_kv_dtype="fp8" combined with {combo} is not implemented on the MI355X path '
+                                              "(only the token step reads FP8 cross-attention K/V)")
         # ---- encoder
         encoder_outputs = kwargs.get("encoder_outputs")
         if encoder_outputs is not None:
@@ -1002,6 +1024,10 @@ class WhisperForConditionalGeneration(nn.Module):
             if frames > 2 * d.max_src or (rt and not force_unique_generate_call):
                 # the reference's seek loop (TF:784-903): with timestamps every window is decoded until its audio is
                 # consumed, also when the input is a single 30 s window (run_pseudo_labelling.py:861-996 calls it so)
+                if cross_kv_dtype is not None:
+                    raise NotImplementedError('cross_kv_dtype="fp8" is implemented for single-window decoding, not inside the '
+                                              "timestamp seek loop (return_timestamps=True without force_unique_generate_call, or "
+                                              "more than 30 s of input), on the MI355X path")
                 if sample_temp is not None:
                     raise NotImplementedError("sampling (a positive temperature as a plain switch) is implemented for "
                                               "single-window decoding, not inside the timestamp seek loop, on the MI355X path "
@@ -1123,12 +1149,13 @@ class WhisperForConditionalGeneration(nn.Module):
             total = P + max_new
             key = (B, total, eos, pad, bool(use_graphs), tuple(suppress or ()), tuple(begin_suppress or ()),
                    None if ts_rules is None else tuple(sorted(ts_rules.items())),
-                   None if soft is None else tuple(sorted((k, v) for k, v in soft.items())))
+                   None if soft is None else tuple(sorted((k, v) for k, v in soft.items())), cross_kv_dtype)
             dec = self._decoders.get(key)
             if dec is None:
                 dec = GreedyDecoder(eng, B, total, eos_token_id=eos, suppress_tokens=suppress,
                                     begin_suppress_tokens=begin_suppress, use_graphs=use_graphs,
-                                    check_every=16 if use_graphs else 1, timestamp_rules=ts_rules, pad_token_id=pad, soft=soft)
+                                    check_every=16 if use_graphs else 1, timestamp_rules=ts_rules, pad_token_id=pad, soft=soft,
+                                    cross_kv_dtype=cross_kv_dtype)
                 self._decoders = {key: dec}        # one live decoder (its graphs pin the K/V cache buffers)
             seqs = dec.run(enc, ids, max_new, min_new)
         else:

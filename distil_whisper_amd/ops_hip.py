@@ -40,14 +40,15 @@ class DwGemm(C.Structure):
 class DwDecoderLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_g", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_g", "ln2_b", "wq", "bq", "wo2", "bo2", "ln3_g", "ln3_b",
-        "w1", "b1", "w2", "b2", "self_kv", "cross_kv")]
+        "w1", "b1", "w2", "b2", "self_kv", "cross_kv", "cross_k8", "cross_v8", "cross_scale")]
 
 
 class DwDecodeStep(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "batch", "n_new", "d_model", "heads", "ffn", "n_layers", "src_len", "max_len", "t", "vocab", "ldv",
         "stream_dtype", "cross_kv_ld")] + [(n, C.c_void_p) for n in (
-            "ids", "tok_emb", "pos_emb", "lnf_g", "lnf_b", "lm_head", "layers", "x", "h", "qkv", "o", "a", "logits")]
+            "ids", "tok_emb", "pos_emb", "lnf_g", "lnf_b", "lm_head", "layers", "x", "h", "qkv", "o", "a", "logits")] + [
+                ("cross_kv_fmt", C.c_int32)]
 
 
 _SIGS = {
@@ -61,6 +62,11 @@ _SIGS = {
                                   C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_float,
                                   C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
     "dw_decode_token_rows": ([C.POINTER(DwDecodeStep), C.c_void_p, C.c_int32, C.c_void_p], C.c_int),
+    "dw_cross_kv_quant": ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+                          C.c_int),
+    "dw_decode_attn_proj_kv8": ([C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float,
+                                 C.c_void_p], C.c_int),
     "dw_slot_step": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int64] +
                      [C.c_void_p] * 7, C.c_int),
     "dw_logmel": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -441,6 +447,26 @@ class HipOps:
                                                     _p(v), k.stride(0), int(kv_rows), _p(kv_app), _p(o), o.stride(0), B, H, float(scale),
                                                     _p(row_t), int(max_t), self._stream()), "decode_attn_proj_rows")
         self._t1(e0, "decode_attn_proj_rows", 0.0)
+        return o
+
+    def cross_kv_quant(self, kv, k8, v8, scales, seq0, n_seq, src_len, H):
+        """FP8 codes and column scales of sequences [seq0, seq0 + n_seq) of a layer from the bf16 K | V rows `kv`
+        [n_seq * src_len, >= 128 H] (dw_cross_kv_quant; the format: include/dwamd.h).  k8, v8 uint8 [B, H, src_len, 64] and scales
+        f32 [B, 2, 64 H] are the layer's whole buffers.  Thin: the library checks the arguments."""
+        e0 = self._t0()
+        self._chk(self.lib.dw_cross_kv_quant(_p(kv), kv.stride(0), _p(k8), _p(v8), _p(scales), int(seq0), int(n_seq), int(src_len),
+                                             int(H), self._stream()), "cross_kv_quant")
+        self._t1(e0, "cross_kv_quant", 0.0)
+
+    def decode_attn_proj_kv8(self, x, ln_g, ln_b, w, bias, k8, v8, scales, B, H, Lk, *, kv_rows=None, eps=1e-5, scale=0.125, out=None):
+        """Mode 0 of `decode_attn_proj` over FP8 K/V (dw_decode_attn_proj_kv8, the launch dw_decode_step makes at cross_kv_fmt = 1):
+        k8, v8 uint8 [B, H, kv_rows, 64] (default kv_rows = Lk), scales f32 [B, 2, 64 H].  Thin: the library checks the arguments."""
+        o = self.empty((B, H * 64), torch.bfloat16) if out is None else out
+        e0 = self._t0()
+        self._chk(self.lib.dw_decode_attn_proj_kv8(_p(x), _dt(x), x.stride(0), _p(ln_g), _p(ln_b), float(eps), _p(w), _p(bias), _p(k8),
+                                                   _p(v8), _p(scales), Lk if kv_rows is None else int(kv_rows), _p(o), o.stride(0), B, H,
+                                                   int(Lk), float(scale), self._stream()), "decode_attn_proj_kv8")
+        self._t1(e0, "decode_attn_proj_kv8", 0.0)
         return o
 
     def decode_token_rows(self, desc, row_t, max_t):

@@ -47,9 +47,20 @@ class PseudoLabeller:
                  timestamp_rules=None, use_graphs=None, rank=0, world=1, suppress_tokens=None,
                  begin_suppress_tokens=None, num_beams=1, overlap=False, decode_cus=64, repetition_penalty=None,
                  no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None, assistant_model=None, num_assistant_tokens=5,
-                 continuous=False, check_every=8):
+                 continuous=False, check_every=8, cross_kv_dtype=None):
         from .longform import history_soft, refuse_continuous
+        from .kv_quant import normalize_dtype
         self.model, self.fe = model, feature_extractor
+        # cross_kv_dtype="fp8": the token loops (GreedyDecoder, SlotDecoder) keep the cross-attention K/V as FP8 codes -- half the
+        # bytes the token step streams; opt-in, the labels may differ where two logits are close.  Only the token step reads
+        # such a cache: the seek loop, beams and an assistant are refused here.
+        cross_kv_dtype = normalize_dtype(cross_kv_dtype)
+        if cross_kv_dtype is not None:
+            for on, what in ((int(num_beams) > 1, "num_beams > 1"), (timestamp_rules is not None, "timestamp_rules (the seek loop)"),
+                             (assistant_model is not None, "an assistant_model")):
+                if on:
+                    raise NotImplementedError(f'PseudoLabeller(cross_kv_dtype="fp8") with {what} is not implemented on the MI355X '
+                                              "path (only the token step reads FP8 cross-attention K/V)")
         self.B, self.max_new = int(batch_size), int(max_new_tokens)
         self.rank, self.world = rank, world
         self.num_beams = int(num_beams)      # generation_num_beams of run_pseudo_labelling.py:835-843
@@ -99,10 +110,10 @@ class PseudoLabeller:
             from .decoding import SlotDecoder
             self.slot_decoder = SlotDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id,
                                             suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                            use_graphs=use_graphs, check_every=check_every)
+                                            use_graphs=use_graphs, check_every=check_every, cross_kv_dtype=cross_kv_dtype)
         self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
                                      suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                     use_graphs=use_graphs, timestamp_rules=timestamp_rules, soft=soft)
+                                     use_graphs=use_graphs, timestamp_rules=timestamp_rules, soft=soft, cross_kv_dtype=cross_kv_dtype)
         self._wave = torch.zeros((self.B, feature_extractor.n_samples), dtype=torch.float32, device=dev)
         # overlap=True: the encoder of the next batch of packs beside the token loop of the current one (longform.two_stage_pipeline;
         # plain greedy decoding only -- the seek loop and beam search encode / decode in their own order)

@@ -457,7 +457,9 @@ typedef struct DwDecoderLayer {
     const void* w2;  const float* b2;    /* fc2 [D][ffn] */
     void* self_kv;               /* bf16 [batch][max_len][2D]: K | V of the generated prefix, appended in place */
     const void* cross_kv;        /* bf16 [batch*src_len][2D]: K | V of the encoder states (projected once per batch); rows
-                                    DwDecodeStep.cross_kv_ld elements apart */
+                                    DwDecodeStep.cross_kv_ld elements apart.  Not read (may be NULL) at cross_kv_fmt = 1 */
+    const void *cross_k8, *cross_v8;   /* cross_kv_fmt = 1: codes uint8 [batch][heads][src_len][64] ("FP8 cross-attention K/V" below) */
+    const float* cross_scale;    /* cross_kv_fmt = 1: float [batch][2][D], K's column scales then V's */
 } DwDecoderLayer;
 typedef struct DwDecodeStep {
     int32_t batch, n_new;        /* n_new new positions per sequence (1 = token step; > 1 = prefill / verify pass) */
@@ -478,6 +480,13 @@ typedef struct DwDecodeStep {
     void *x, *h, *qkv, *o, *a;   /* workspace, rows = batch*n_new: x [rows][D] stream dtype; h, o [rows][D], qkv
                                     [rows][3D], a [rows][ffn] bf16 */
     void* logits;                /* out: bf16 [rows][ldv] */
+    int32_t cross_kv_fmt;        /* 0: the cross-attention reads DwDecoderLayer.cross_kv (bf16) -- the pass as it always was.
+                                    1: it reads cross_k8 / cross_v8 / cross_scale through dw_decode_attn_proj_kv8, for every layer;
+                                    every other launch of the pass is unchanged.  Only the token step has that kernel: n_new > 1,
+                                    dw_decode_step_rows, a d_model outside 384 / 512 / 768 / 1024 / 1280, src_len > 8192 or
+                                    dw_debug_set key 7 bit 3 set are DW_EUNSUP, a NULL cross_k8 / cross_v8 / cross_scale / bq /
+                                    ln2_g / ln2_b of any layer, a cross_k8 / cross_v8 not 16-byte or a cross_scale not 4-byte aligned,
+                                    and any other value of the field DW_EINVAL, before any launch. */
 } DwDecodeStep;
 int dw_decode_step(const DwDecodeStep* d, void* stream);
 /* dw_decode_step_rows: the same pass with row b of the batch starting at position row_t[b] instead of d->t (which is ignored):
@@ -527,6 +536,49 @@ int dw_decode_attn_proj(int mode, const void* x, int x_dtype, int64_t ldx, const
 int dw_decode_attn_proj_rows(const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps, const void* w,
                              const float* bias, const void* k, const void* v, int64_t ldkv, int64_t kv_rows, void* kv_app, void* o,
                              int64_t ldo, int B, int H, float scale, const int32_t* row_t, int32_t max_t, void* stream);
+/* ---- FP8 cross-attention K/V (opt-in; the format is stated here and nowhere else) -------------------------------------------
+ * Scope of a scale: one sequence b, one layer, one tensor (K or V), one column c < D, over the src_len rows j of that sequence.
+ *   amax = max_j |x[b][j][c]|                                   over the bf16 values
+ *   inv  = 448 / amax,  s = amax / 448                          two fp32 round-to-nearest divisions;  amax < 2^-100 (zero included):
+ *                                                               inv = s = 1 -- the column counts as zero, its codes are signed zeros,
+ *                                                               and 448 / amax is finite for every other column
+ *   code = e4m3fn(x * inv)                                      fp32 product (not contracted with anything), rounded to nearest
+ *                                                               even onto the OCP e4m3fn grid (4 exponent bits, bias 7, 3 mantissa
+ *                                                               bits, subnormals of 2^-9, no infinities), saturated at +-448: never
+ *                                                               a NaN code; the sign of a zero is kept
+ *   value the kernels use = s * float(code)
+ * The scales are per COLUMN: K's fold into the query and V's into the output once per workgroup, no scale is read per key, and an
+ * outlier channel does not cost the other columns their precision.
+ * Layout of a layer: codes head-major, uint8 [B][H][src_len][64] for K and for V (a (sequence, head) workgroup streams one
+ * contiguous region whose 128-byte lines are wholly its own); scales float [B][2][D], K's D columns then V's.
+ *
+ * dw_cross_kv_quant: codes and scales of sequences [seq0, seq0 + n_seq) of a layer from the bf16 K | V rows the projection GEMM
+ * writes: kv [n_seq * src_len][ld], K in columns [0, D), V in [D, 2D), D = 64 * H; row j of sequence seq0 + i is row i * src_len + j.
+ * k8, v8, scales: the layer's whole buffers (sequence 0 first).  One launch, two sweeps (column maxima, then codes; the second reads
+ * from L2).  Only the addressed sequences' codes and scales are written.  Checked before the launch, in this order:
+ *   DW_EINVAL  a null kv, k8, v8 or scales;  seq0 < 0, n_seq < 1, src_len < 1, H < 1;
+ *              kv not 16-byte aligned or ld not a multiple of 8 elements, k8 / v8 not 8-byte, scales not 4-byte aligned
+ *   DW_EUNSUP  n_seq > 65535, H > 16384 (grid dimensions)
+ *   DW_EINVAL  ld < 2D
+ * A refused call launches nothing and writes nothing.  Nothing is allocated, nothing synchronises. */
+int dw_cross_kv_quant(const void* kv, int64_t ld, void* k8, void* v8, float* scales, int seq0, int n_seq, int src_len, int H,
+                      void* stream);
+/* dw_decode_attn_proj_kv8: mode 0 of dw_decode_attn_proj over FP8 K/V, alone -- the launch dw_decode_step makes for a layer's
+ * cross-attention at cross_kv_fmt = 1.  LayerNorm and q projection are those of dw_decode_attn_proj, sum for sum: q is the same
+ * bf16 value, bit for bit.  With sK = kv_scale[b][0], sV = kv_scale[b][1], c = scale * log2(e):
+ *   score_j = sum_d (q_d * c * sK_d) * float(k8[b][h][j][d])      fp32
+ *   o[b][h][d] = bf16(sV_d * (sum_j bf16(P_j) * float(v8[b][h][j][d]) / sum_j P_j)),  P_j = exp2(score_j - max score)
+ * k8, v8: uint8 [B][H][kv_rows][64], the first Lk rows of a head are read; kv_scale float [B][2][D]; o bf16 [B][ldo].
+ * Checked before any launch, in this order:
+ *   DW_EINVAL  x_dtype not DW_F32 / DW_BF16; a null x, ln_g, ln_b, w, bias, k8, v8, kv_scale, o; B < 1, H < 1, Lk < 1, Lk > kv_rows;
+ *              x, w, k8, v8, ln_g or ln_b not 16-byte aligned, ldx not a multiple of 8 elements; bias or kv_scale not 4-byte, o
+ *              not 2-byte aligned
+ *   DW_EUNSUP  B or H above 65535; D = 64 * H not one of 384 / 512 / 768 / 1024 / 1280; Lk > 8192
+ *   DW_EINVAL  ldx < D, ldo < D
+ * A refused call launches nothing and writes nothing.  One launch on `stream`; nothing is allocated, nothing synchronises. */
+int dw_decode_attn_proj_kv8(const void* x, int x_dtype, int64_t ldx, const float* ln_g, const float* ln_b, float eps, const void* w,
+                            const float* bias, const void* k8, const void* v8, const float* kv_scale, int64_t kv_rows, void* o,
+                            int64_t ldo, int B, int H, int Lk, float scale, void* stream);
 /* dw_decode_token_rows: the token step (n_new == 1, else DW_EINVAL) with row b at position row_t[b] (row_t / max_t as for
  * dw_decode_step_rows): the launch sequence of dw_decode_step at n_new == 1 with two launches swapped -- the embedding takes the
  * position row per sequence, the self-attention with its projection and K/V append inside is dw_decode_attn_proj_rows.  With equal
