@@ -449,15 +449,20 @@ class GreedyDecoder:
 
 
 def slot_step_torch(logits, V, tokens, length, plen, budget, done, row_t, cur, *, suppress=None, begin_suppress=None,
-                    timestamp_rules=None, eos=None, min_new=0):
+                    timestamp_rules=None, eos=None, min_new=0, lp_sum=None, nsp=None, nsp_pos=None, nsp_col=-1):
     """The slot step of continuous batching as torch ops and host arithmetic (`dw_slot_step`, csrc/slots.hip, is the kernel;
     include/dwamd.h states the rule): the path of oracle.ref_ops and the CPU.  logits [S, >= V]: row b is the output of the pass
     that fed cur[b] at position row_t[b]; tokens int64 [S, max_len]; length / plen / budget / row_t int32 [S]; done bool [S]; cur
     int64 [S, 1]; all updated in place.  A done slot is parked at position 0; inside its prompt a slot takes the forced token;
     otherwise the argmax of `processed_scores` with the slot's own history, begin_index = plen[b], first = (len == plen), no_eos =
-    (len - plen < min_new); a generated EOS or a spent budget ends the slot."""
+    (len - plen < min_new); a generated EOS or a spent budget ends the slot.  With `lp_sum` (f32 [S]; `dw_slot_step_scores`): a
+    generated step adds log_softmax(processed scores)[nxt] to lp_sum[b] (a row with no allowed column adds nothing), and with
+    nsp_col >= 0 the step whose row is the output of input position nsp_pos[b] writes softmax(row)[nsp_col] into nsp[b] -- of the
+    raw row when that step is forced, of the processed scores when it is generated; a parked slot keeps both."""
     lens, pls, buds, dns = length.tolist(), plen.tolist(), budget.tolist(), done.tolist()
     rules = None if timestamp_rules is None else dict(timestamp_rules)
+    want_nsp = lp_sum is not None and int(nsp_col) >= 0
+    at = nsp_pos.tolist() if want_nsp else None
     for b in range(tokens.shape[0]):
         n, P = lens[b], pls[b]
         if dns[b] or n < 1 or n >= tokens.shape[1] or P < 1:
@@ -468,10 +473,17 @@ def slot_step_torch(logits, V, tokens, length, plen, budget, done, row_t, cur, *
         forced = n < P
         if forced:
             nxt = int(tokens[b, n])
+            if want_nsp and n - 1 == at[b]:
+                nsp[b] = torch.softmax(logits[b, :V].float(), -1)[int(nsp_col)]
         else:
             sc = processed_scores(logits[b:b + 1, :V], tokens[b:b + 1], n, begin_index=P, eos=eos, no_eos=n - P < int(min_new),
                                   first=n == P, suppress=suppress, begin_suppress=begin_suppress, timestamp_rules=rules)
             nxt = int(sc.argmax(-1))
+            if lp_sum is not None and bool(torch.isfinite(sc[0, nxt])):
+                lsm = torch.log_softmax(sc[0].float(), -1)
+                lp_sum[b] += lsm[nxt]
+                if want_nsp and n - 1 == at[b]:
+                    nsp[b] = lsm[int(nsp_col)].exp()
         tokens[b, n] = nxt
         length[b] = n + 1
         if not forced and ((eos is not None and nxt == eos) or n + 1 >= buds[b]):
@@ -499,13 +511,26 @@ class SlotDecoder:
 
     run(windows): `windows` iterates (key, enc_rows, prompt_ids, max_new_tokens) -- enc_rows: the window's encoder output rows
     (engine layout), prompt_ids: P >= 1 ids (list or 1-D tensor), max_new_tokens >= 1 with P + max_new_tokens <= max_len.  Yields
-    (key, row) as rows finish, row int64 = prompt + generated tokens up to and including EOS.  `steps` counts executed token steps."""
+    (key, row) as rows finish, row int64 = prompt + generated tokens up to and including EOS.  `steps` counts executed token steps.
+    The source may yield `SlotDecoder.WAIT` -- "nothing now, but more may come once a live row has ended" (the seek loop: an
+    utterance's next window is known only when the previous one is done): the empty slots stay empty until the next look, when
+    the source is asked again; `run` ends when the source is exhausted and every slot is empty.
+
+    scores=True: the slot step is dw_slot_step_scores and `run` yields (key, row, lp_sum, nsp) -- the sum of the generated tokens'
+    log-probabilities under the processed scores and, with `nsp_col` (the <|nospeech|> id), softmax(row)[nsp_col] of the row behind
+    input position `nsp_pos`, the optional fifth entry of a window (default: prompt length - 1, the first generated step)."""
     BUCKET = 64
+    WAIT = object()
 
     def __init__(self, engine, slots, max_len, eos_token_id, suppress_tokens=None, begin_suppress_tokens=None, timestamp_rules=None,
-                 min_new_tokens=0, pad_token_id=None, use_graphs=None, check_every=8, cross_kv_dtype=None):
+                 min_new_tokens=0, pad_token_id=None, use_graphs=None, check_every=8, cross_kv_dtype=None, scores=False,
+                 nsp_col=None):
         self.eng, self.S, self.max_len = engine, int(slots), int(max_len)
         d = engine.dims
+        self.scores = bool(scores)
+        self.nsp_col = -1 if nsp_col is None else int(nsp_col)
+        if self.nsp_col >= d.vocab or (self.nsp_col >= 0 and not self.scores):
+            raise ValueError("nsp_col names a column of the vocabulary and needs scores=True")
         self.cross_kv_dtype = kv_quant.normalize_dtype(cross_kv_dtype)      # "fp8": see GreedyDecoder
         if self.cross_kv_dtype is not None:
             kv_quant.check_width(d.d_model)
@@ -528,8 +553,9 @@ class SlotDecoder:
         self.tokens = torch.zeros((S, self.max_len), dtype=torch.long, device=dev)
         self.cur = torch.zeros((S, 1), dtype=torch.long, device=dev)
         self.done = torch.ones((S,), dtype=torch.bool, device=dev)
-        self.state = torch.ones((4, S), dtype=torch.int32, device=dev)          # rows: len, plen, budget, row_t
-        self.len, self.plen, self.budget, self.row_t = self.state[0], self.state[1], self.state[2], self.state[3]
+        self.state = torch.ones((5, S), dtype=torch.int32, device=dev)          # rows: len, plen, budget, row_t, nsp_pos
+        self.len, self.plen, self.budget, self.row_t, self.nsp_pos = (self.state[i] for i in range(5))
+        self.sc = torch.zeros((2, S), dtype=torch.float32, device=dev)          # rows: lp_sum, nsp (scores=True)
         self.cache = None
         self.graphs = {}
         self.pool = None
@@ -540,16 +566,17 @@ class SlotDecoder:
         eng, V = self.eng, self.eng.dims.vocab
         logits = eng.decode_token_rows(self.cur, self.cache, self.row_t, max_t)
         r = self.timestamp_rules
+        sc = dict(lp_sum=self.sc[0], nsp=self.sc[1], nsp_pos=self.nsp_pos, nsp_col=self.nsp_col) if self.scores else {}
         if hasattr(eng.ops, "slot_step"):
             mi = None if r is None else r.get("max_initial_timestamp_index")
             eng.ops.slot_step(logits, V, self.tokens, self.len, self.plen, self.budget, self.done, self.row_t, self.cur,
                               suppress=self.suppress, begin_suppress=self.begin_suppress,
                               ts_begin=-1 if r is None else int(r["no_timestamps_token_id"]) + 1, max_initial=-1 if mi is None else int(mi),
-                              eos=self.eos, min_new=self.min_new)
+                              eos=self.eos, min_new=self.min_new, **sc)
         else:
             slot_step_torch(logits, V, self.tokens, self.len, self.plen, self.budget, self.done, self.row_t, self.cur,
                             suppress=self.suppress, begin_suppress=self.begin_suppress, timestamp_rules=r, eos=self.eos,
-                            min_new=self.min_new)
+                            min_new=self.min_new, **sc)
 
     def _run_step(self, bound):
         # the pass is launched with the bucket's last position as max_t: it places the kernels' LDS regions only
@@ -563,9 +590,10 @@ class SlotDecoder:
         if g is None:
             if not self._warm:
                 # one eager step first: lazy initialisation inside torch must not happen under stream capture
-                keep = (self.cur.clone(), self.tokens.clone(), self.done.clone(), self.state.clone())
+                keep = (self.cur.clone(), self.tokens.clone(), self.done.clone(), self.state.clone(), self.sc.clone())
                 self._step(max_t)
                 self.cur.copy_(keep[0]); self.tokens.copy_(keep[1]); self.done.copy_(keep[2]); self.state.copy_(keep[3])
+                self.sc.copy_(keep[4])
                 torch.cuda.synchronize(self.dev)
                 self.pool = torch.cuda.graph_pool_handle()
                 self._warm = True
@@ -575,7 +603,7 @@ class SlotDecoder:
             self.graphs[bucket] = g
         g.replay()
 
-    def _refill(self, b, enc_rows, prompt, max_new):
+    def _refill(self, b, enc_rows, prompt, max_new, nsp_pos=None):
         prompt = torch.as_tensor(prompt, dtype=torch.long).reshape(-1)
         P, max_new = int(prompt.numel()), int(max_new)
         if P < 1 or max_new < 1 or P + max_new > self.max_len:
@@ -583,7 +611,10 @@ class SlotDecoder:
                              f"{self.max_len} (got {P} + {max_new})")
         self.eng.decode_refill(self.cache, b, enc_rows)
         self.tokens[b, :P] = prompt.to(self.dev)
-        self.state[:, b] = torch.tensor([1, P, P + max_new, 0], dtype=torch.int32).to(self.dev)
+        self.state[:, b] = torch.tensor([1, P, P + max_new, 0, P - 1 if nsp_pos is None else int(nsp_pos)],
+                                        dtype=torch.int32).to(self.dev)
+        if self.scores:
+            self.sc[:, b] = 0.0
         self.cur[b, 0] = self.tokens[b, 0]
         self.done[b] = False
 
@@ -596,27 +627,80 @@ class SlotDecoder:
         it = iter(windows)
         while True:
             dn, ln = self.done.tolist(), self.len.tolist()          # the loop's only synchronisation
+            sc = self.sc.tolist() if self.scores else None
             for b in range(S):
                 if keys[b] is not None and dn[b]:
-                    yield keys[b], self.tokens[b, :ln[b]].clone()
-                    keys[b] = None
+                    row = self.tokens[b, :ln[b]].clone()
+                    key, keys[b] = keys[b], None
+                    yield (key, row, sc[0][b], sc[1][b]) if self.scores else (key, row)
             bound = 0
+            waiting = False                           # the source has answered WAIT at this look: it is asked again at the next
             for b in range(S):
-                if keys[b] is None and it is not None:
+                if keys[b] is None and it is not None and not waiting:
                     w = next(it, None)
                     if w is None:
                         it = None
+                    elif w is self.WAIT:
+                        waiting = True
                     else:
                         keys[b] = w[0]
-                        self._refill(b, w[1], w[2], w[3])
+                        self._refill(b, *w[1:5])
                         ln[b] = 1
                 if keys[b] is not None:
                     bound = max(bound, ln[b] - 1)
             if all(k is None for k in keys):
+                if waiting:
+                    raise RuntimeError("the window source answered WAIT with every slot empty: no live row can bring it a window")
                 return
             for _ in range(self.check_every):
                 self._run_step(min(bound, self.max_len - 1))
                 bound += 1
+
+
+class SeekWindowSource:
+    """The window source of the timestamp seek loop on slots (modeling.seek_decode `slots=N`): an utterance's next window is
+    known only when its previous one has ended, so the source keeps `fresh` (utterances not yet started), `cont` (utterances whose
+    next window is known: encoded before any fresh one) and `ready` (encoded windows no slot has taken).  Asked for a window with
+    `ready` empty it encodes up to N known windows in ONE call -- encode(utterances) -> [n, max_src, d_model] --, so at most 2 N
+    encoded windows exist: N in slots, N ready.  With no window known and windows still inside slots it answers
+    `SlotDecoder.WAIT`; with none inside slots either it is exhausted.  job(b, k) -> (prompt, max_new_tokens, nsp_pos) of
+    utterance b's k-th window.  The consumer calls `ended(b, more)` for every window `SlotDecoder.run` hands back, before it asks
+    for the next one.  `stats`: the encoder calls' batch sizes, the most encoded windows held, the windows ended."""
+
+    def __init__(self, utterances, slots, encode, job):
+        from collections import deque
+        self.N, self.encode, self.job = int(slots), encode, job
+        self.fresh, self.cont, self.ready = deque(utterances), deque(), deque()
+        self.taken = {}                                # windows of utterance b handed to a slot
+        self.live = 0
+        self.stats = dict(steps=0, encoder_batches=[], max_held=0, windows=0)
+
+    def ended(self, b, more):
+        self.live -= 1
+        self.stats["windows"] += 1
+        if more:
+            self.cont.append(b)
+
+    def __iter__(self):
+        while True:
+            if not self.ready:
+                take = []
+                while len(take) < self.N and (self.cont or self.fresh):
+                    take.append(self.cont.popleft() if self.cont else self.fresh.popleft())
+                if not take:
+                    if not self.live:
+                        return
+                    yield SlotDecoder.WAIT
+                    continue
+                enc = self.encode(take)
+                self.stats["encoder_batches"].append(len(take))
+                self.ready.extend((b, enc[i]) for i, b in enumerate(take))
+                self.stats["max_held"] = max(self.stats["max_held"], len(self.ready) + self.live)
+            b, rows = self.ready.popleft()
+            k = self.taken.get(b, 0)
+            self.taken[b] = k + 1
+            self.live += 1
+            yield (b, rows) + tuple(self.job(b, k))
 
 
 # DW_ASSIST_TORCH=1 (read when an assisted decode starts): the round stays on the torch ops of `assist_pick_torch` / `assist_accept_torch`

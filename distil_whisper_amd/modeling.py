@@ -807,7 +807,8 @@ class WhisperForConditionalGeneration(nn.Module):
                  temperature=None, compression_ratio_threshold=None, logprob_threshold=None, no_speech_threshold=None,
                  num_segment_frames=None, attention_mask=None, time_precision=0.02, time_precision_features=0.01,
                  return_token_timestamps=None, return_segments=False, return_dict_in_generate=None,
-                 force_unique_generate_call=None, monitor_progress=None, *, use_graphs=None, cross_kv_dtype=None, **kwargs):
+                 force_unique_generate_call=None, monitor_progress=None, *, use_graphs=None, cross_kv_dtype=None, seek_slots=None,
+                 **kwargs):
         """`WhisperGenerationMixin.generate` (TF:generation_whisper.py:383-968) on the MI355X engine, with the argument
         list of the reference (run_distillation.py:1524-1528, run_eval.py:690-739, 806-844): greedy search over one
         30 s window per row with language / task / timestamp / prompt_ids prefixes, the suppress / begin-suppress /
@@ -858,6 +859,14 @@ class WhisperForConditionalGeneration(nn.Module):
         and the repetition / bias options.  The seek loop, `num_beams > 1`, an `assistant_model`, `output_scores` /
         `output_logits` and `return_token_timestamps` RAISE NotImplementedError before the encoder runs; `use_cache=False`, any
         other value and a model width without the kernel are a ValueError.
+        `seek_slots=N` (with `return_timestamps=True`, inputs of any length): the seek loop's windows as jobs of a
+        decoding.SlotDecoder of N slots (seek_decode `slots`) -- an utterance's next window takes a free slot as soon as the
+        previous one has ended, the token steps replay from a HIP graph, `cross_kv_dtype="fp8"` is allowed, and
+        `logprob_threshold` / `no_speech_threshold` are judged on numbers the slot step keeps (dw_slot_step_scores) instead of a
+        teacher-forced pass.  Greedy at temperature 0: with a positive temperature, `condition_on_prev_tokens`, beams, an
+        assistant, `return_token_timestamps`, the history / bias rules, `use_cache=False`, `output_scores` / `output_logits` or
+        `decoder_input_ids` it RAISES NotImplementedError before the encoder runs; without `return_timestamps` or below 1 a
+        ValueError.
         Returns what the reference returns: the generated tokens only (decoder prompt and EOS stripped, right-padded
         with pad_token_id), or with `return_dict_in_generate=True` / `force_unique_generate_call=True` the full
         sequences (prompt + generated, as GenerationMixin emits them)."""
@@ -890,6 +899,31 @@ class WhisperForConditionalGeneration(nn.Module):
         num_beams = int(getattr(gc, "num_beams", 1) or 1)
         if num_beams > 1 and (getattr(gc, "num_beam_groups", 1) or 1) != 1:
             raise NotImplementedError("group beam search is not implemented on the MI355X path")
+        # ---- seek_slots=N: the timestamp seek loop as a slot schedule (seek_decode `slots`); everything it does not run is
+        # refused here, before the encoder runs
+        if seek_slots is not None:
+            rt_ = return_timestamps if return_timestamps is not None else bool(getattr(gc, "return_timestamps", False))
+            if not rt_ or force_unique_generate_call or kwargs.get("encoder_outputs") is not None:
+                raise ValueError("seek_slots schedules the timestamp seek loop: it needs return_timestamps=True and input_features "
+                                 "(not force_unique_generate_call or encoder_outputs)")
+            if isinstance(seek_slots, bool) or int(seek_slots) < 1:
+                raise ValueError("seek_slots is the number of slots, at least 1")
+            for on, combo in ((any(t is not None and float(t) > 0.0 for t in temps), "a positive temperature"),
+                              (bool(condition_on_prev_tokens), "condition_on_prev_tokens"),
+                              (num_beams > 1, "beam search (num_beams > 1)"),
+                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
+                              (bool(return_token_timestamps), "return_token_timestamps"),
+                              (getattr(gc, "repetition_penalty", None) not in (None, 1.0) or
+                               bool(int(getattr(gc, "no_repeat_ngram_size", 0) or 0)) or
+                               getattr(gc, "sequence_bias", None) is not None or getattr(gc, "bad_words_ids", None) is not None,
+                               "repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids"),
+                              (kwargs.get("use_cache", True) is False, "use_cache=False"),
+                              (bool(getattr(gc, "output_scores", False)) or bool(getattr(gc, "output_logits", False)),
+                               "output_scores / output_logits"),
+                              (kwargs.get("decoder_input_ids") is not None, "decoder_input_ids")):
+                if on:
+                    raise NotImplementedError(f"seek_slots combined with {combo} is not implemented on the MI355X path (the slot "
+                                              "step decodes the seek loop's windows greedily at temperature 0)")
         if (getattr(gc, "num_return_sequences", 1) or 1) != 1:
             raise NotImplementedError("num_return_sequences > 1 is not implemented on the MI355X path")
         if num_beams == 1 and getattr(gc, "length_penalty", None) not in (None, 1.0):
@@ -989,7 +1023,8 @@ class WhisperForConditionalGeneration(nn.Module):
                               (kwargs.get("assistant_model") is not None, "an assistant_model"),
                               (want_scores or want_logits, "output_scores / output_logits"),
                               (bool(return_token_timestamps), "return_token_timestamps"),
-                              (uses_fallback, "the temperature fallback / condition_on_prev_tokens (the seek loop)")):
+                              (uses_fallback and seek_slots is None,
+                               "the temperature fallback / condition_on_prev_tokens (the seek loop)")):
                 if on:
                     raise NotImplementedError(f'cross_kv_dtype="fp8" combined with {combo} is not implemented on the MI355X path '
                                               "(only the token step reads FP8 cross-attention K/V)")
@@ -1024,7 +1059,7 @@ class WhisperForConditionalGeneration(nn.Module):
             if frames > 2 * d.max_src or (rt and not force_unique_generate_call):
                 # the reference's seek loop (TF:784-903): with timestamps every window is decoded until its audio is
                 # consumed, also when the input is a single 30 s window (run_pseudo_labelling.py:861-996 calls it so)
-                if cross_kv_dtype is not None:
+                if cross_kv_dtype is not None and seek_slots is None:
                     raise NotImplementedError('cross_kv_dtype="fp8" is implemented for single-window decoding, not inside the '
                                               "timestamp seek loop (return_timestamps=True without force_unique_generate_call, or "
                                               "more than 30 s of input), on the MI355X path")
@@ -1044,7 +1079,9 @@ class WhisperForConditionalGeneration(nn.Module):
                                                 prompt_ids, kwargs, use_graphs, return_dict_in_generate, num_beams,
                                                 fallback_args, return_segments, token_ts,
                                                 history=dict(repetition_penalty=rp, no_repeat_ngram_size=nrn,
-                                                             sequence_bias=bias_table))
+                                                             sequence_bias=bias_table),
+                                                seek_slots=None if seek_slots is None else dict(
+                                                    slots=int(seek_slots), cross_kv_dtype=cross_kv_dtype, use_graphs=use_graphs))
             if return_segments:
                 raise NotImplementedError("return_segments comes with the timestamp seek loop (return_timestamps=True) "
                                           "on the MI355X path")
@@ -1205,7 +1242,7 @@ class WhisperForConditionalGeneration(nn.Module):
                     no_speech_threshold=None, condition_on_prev_tokens=False, prev_sot_token_id=None, prompt_ids=None,
                     prompt_all_segments=False, num_beams=1, length_penalty=1.0, early_stopping=False, assistant=None,
                     num_assistant_tokens=5, token_timestamps=None, repetition_penalty=None, no_repeat_ngram_size=0,
-                    sequence_bias=None):
+                    sequence_bias=None, slots=None, check_every=8, cross_kv_dtype=None, use_graphs=None):
         """The seek loop itself (TF:generation_whisper.py:784-903): input_features [B, n_mels, frames], max_frames[b] =
         valid mel frames of utterance b.  init_tokens: the decoder prompt rows (list of B lists) or a callable(detect)
         building them (detect() = language ids from the first window); lengths(P) -> (max_new_tokens, min_new_tokens)
@@ -1258,6 +1295,18 @@ class WhisperForConditionalGeneration(nn.Module):
             the greedy pass of a window applies the table inside the selection kernel (dw_greedy_select_bias), the sampled
             fallback passes and the threshold scores apply it as torch ops through `processed` (the sampling kernel takes no
             table).  Not with token timestamps.
+          * slots=N (None: the lockstep loop above, pass by pass): the same windows as jobs of a decoding.SlotDecoder of N slots.
+            Every (utterance, window) is decoded by the slot step with the timestamp rules at the slot's own position; when a
+            window ends, `retrieve_segment` tells the utterance's next window, which joins the windows still to encode
+            (continuations before utterances not yet started).  The encoder runs when no encoded window is waiting, over up to
+            N windows in one call, so at most 2 N encoded windows exist (N in slots, N waiting).  A short tail window therefore
+            waits for no longer row of its pass, the token steps replay from a HIP graph (`use_graphs`), and
+            `cross_kv_dtype="fp8"` keeps the slots' cross-attention K/V as FP8 codes.  With the thresholds the slot step itself
+            keeps each window's log-probability sum and no-speech probability (dw_slot_step_scores): no teacher-forced pass.
+            Greedy, temperature 0 only: a positive temperature, condition_on_prev_tokens, beams, an assistant, token timestamps,
+            the history / bias rules raise NotImplementedError before the encoder runs, as do `init_tokens` rows of different
+            lengths.  `last_seek_stats` holds the token steps, the encoder calls' batch sizes and the most encoded windows held;
+            `last_window_scores` (either loop, with a threshold) the numbers every window was judged by.
         -> per utterance the list of segments {"start", "end", "tokens"}."""
         import math
         import zlib
@@ -1265,6 +1314,26 @@ class WhisperForConditionalGeneration(nn.Module):
         from .decoding import SAMPLE_TORCH_ENV, GreedyDecoder, processed_scores, token_mask
         eng, d = self.engine, self.dims
         B = input_features.shape[0]
+        if slots is None:
+            if cross_kv_dtype is not None or use_graphs is not None:
+                raise ValueError("seek_decode: cross_kv_dtype / use_graphs belong to the slot schedule (slots=N)")
+        else:
+            if int(slots) < 1 or int(check_every) < 1:
+                raise ValueError("seek_decode(slots=N) needs N >= 1 slots and check_every >= 1")
+            _t = temperatures if isinstance(temperatures, (list, tuple)) else [temperatures]
+            for on, what in ((any(x is not None and float(x) > 0.0 for x in _t), "a positive temperature (sampled fallback passes)"),
+                             (bool(condition_on_prev_tokens), "condition_on_prev_tokens"),
+                             (int(num_beams) > 1, "num_beams > 1"),
+                             (assistant is not None, "an assistant_model"),
+                             (token_timestamps is not None, "return_token_timestamps"),
+                             (repetition_penalty not in (None, 1.0) or bool(no_repeat_ngram_size) or sequence_bias is not None,
+                              "repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids")):
+                if on:
+                    raise NotImplementedError(f"the timestamp seek loop on slots (seek_slots / slots=N) with {what} is not "
+                                              "implemented on the MI355X path (the slot step decodes greedily at temperature 0)")
+            if not callable(init_tokens) and len({len(r) for r in init_tokens}) > 1:
+                raise NotImplementedError("the timestamp seek loop on slots needs decoder prompts of one length (init_tokens rows "
+                                          "of different lengths)")
         rep_pen = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
         ngram = int(no_repeat_ngram_size or 0)
         hist_soft = None
@@ -1437,6 +1506,86 @@ class WhisperForConditionalGeneration(nn.Module):
         if not hasattr(self, "_seek_decoders"):
             self._seek_decoders = {}           # reused by later calls (pseudo-labelling decodes batch after batch)
         decoders = self._seek_decoders
+        # (utterance, first frame, average log-probability, no-speech probability) of every scored pass over a window, in order
+        window_scores = self.last_window_scores = []
+
+        def strip_pad(seq):
+            if seq and seq[-1] == pad:     # TF:1064-1071: drop the padding (all but one EOS when pad == EOS)
+                npad = sum(1 for x in seq if x == pad) - (1 if pad == eos else 0)
+                if npad:
+                    seq = seq[:-npad]
+            return seq
+
+        def judge(gen, avg, nsp):
+            """(decode again at the next temperature, skip the window) of one decoded window (TF:1243-1287)."""
+            fallback = skip = False
+            if compression_ratio_threshold is not None and gen and ratio(gen) > compression_ratio_threshold:
+                fallback = True
+            if logprob_threshold is not None and avg < logprob_threshold:
+                fallback = True
+            if no_speech_threshold is not None and avg < logprob_threshold and nsp > no_speech_threshold:
+                fallback, skip = False, True
+            return fallback, skip
+
+        if slots is not None:
+            # ---- the seek loop as a slot schedule: every (utterance, window) is a SlotDecoder job
+            from .decoding import SeekWindowSource, SlotDecoder
+            N = int(slots)
+            if callable(init_tokens) and len({len(r) for r in init}) > 1:      # (given rows were judged before the encoder ran)
+                raise NotImplementedError("the timestamp seek loop on slots needs decoder prompts of one length (init_tokens rows "
+                                          "of different lengths)")
+            P = len(prompt or []) + P0
+            per_pass = []                  # lengths(P) of an utterance's k-th window: the lockstep loop asks once per pass
+
+            def job(b, k):
+                while len(per_pass) <= k:
+                    per_pass.append(lengths(P))
+                if per_pass[k][1] != per_pass[0][1]:
+                    raise NotImplementedError("the timestamp seek loop on slots needs one min_new_tokens for every window")
+                return (prompt or []) + list(init[b]), per_pass[k][0], P - P0
+
+            def encode(take):
+                enc, _ = eng.encode(window(take), save=False)
+                return enc[:len(take) * d.max_src].view(len(take), d.max_src, -1)
+            job(0, 0)
+            min_new = per_pass[0][1]
+            key = ("slots", N, eos, pad, nts, max_initial_timestamp_index, tuple(suppress_tokens or ()),
+                   tuple(begin_suppress_tokens or ()), min_new, int(check_every), cross_kv_dtype, use_graphs, need_scores)
+            # Slot decoders are kept apart from the lockstep loop's (whose many batch sizes must not push them out).  Each owns its
+            # K/V caches -- N slots x (max_target_positions self rows + max_source_positions cross rows) x 2 d_model per decoder
+            # layer: 0.6 GB per layer at 64 slots of d_model 1280 in bf16, 20 GB for large-v3's 32 layers -- and its graphs, so
+            # only `seek_slot_decoders_max` (2: one configuration and a variant) stay alive; set the attribute to keep more.
+            slot_decoders = self.__dict__.setdefault("_seek_slot_decoders", {})
+            dec = slot_decoders.get(key)
+            if dec is None:
+                while len(slot_decoders) >= max(1, int(getattr(self, "seek_slot_decoders_max", 2))):
+                    slot_decoders.pop(next(iter(slot_decoders)))
+                dec = slot_decoders[key] = SlotDecoder(
+                    eng, N, d.max_tgt, eos, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+                    timestamp_rules=ts_rules, min_new_tokens=min_new, pad_token_id=pad, use_graphs=use_graphs,
+                    check_every=check_every, cross_kv_dtype=cross_kv_dtype, scores=need_scores,
+                    nsp_col=nts - 1 if need_scores else None)
+            source = SeekWindowSource([b for b in range(B) if seek[b] < max_frames[b]], N, encode, job)
+            steps0 = dec.steps
+            for res in dec.run(source):
+                b, seq = res[0], strip_pad(res[1][P:].tolist())
+                avg = nsp = None
+                if need_scores:
+                    avg, nsp = (float(res[2]) / len(seq) if seq else 0.0), float(res[3])
+                    window_scores.append((b, seek[b], avg, nsp))
+                _, skip = judge(seq, avg, nsp)         # (one temperature: nothing to fall back to)
+                snf = min(max_frames[b] - seek[b], W)
+                if skip:
+                    seek[b] += snf
+                else:
+                    segs, offset = G.retrieve_segment(seq[:-1] if (seq and seq[-1] == eos) else seq, tb, snf,
+                                                      time_offset=seek[b] * 0.01, with_idxs=False)
+                    seek[b] += offset
+                    segments[b] += segs
+                source.ended(b, seek[b] < max_frames[b])
+            self.last_seek_stats = dict(source.stats, steps=dec.steps - steps0)
+            return [sg[1:] for sg in segments] if first_segment_prompt else segments
+
         while any(seek[b] < max_frames[b] for b in range(B)):
             rows = [b for b in range(B) if seek[b] < max_frames[b]]
             snf = {b: min(max_frames[b] - seek[b], W) for b in rows}
@@ -1522,28 +1671,17 @@ class WhisperForConditionalGeneration(nn.Module):
                             for i, b in enumerate(pending):
                                 window_ts[b] = ts[i]
                         out = full[:, P:].tolist()
-                    gens = []
-                    for seq in out:
-                        if seq and seq[-1] == pad:     # TF:1064-1071: drop the padding (all but one EOS when pad == EOS)
-                            npad = sum(1 for x in seq if x == pad) - (1 if pad == eos else 0)
-                            if npad:
-                                seq = seq[:-npad]
-                        gens.append(seq)
+                    gens = [strip_pad(seq) for seq in out]
                     avg = nsp = None
                     if need_scores and temp == 0.0 and int(num_beams) > 1 and assistant is None:
                         avg, nsp = beam_scored           # the hypotheses' own scores: no teacher-forced pass (TF:1261-1264)
                     elif need_scores:
                         avg, nsp = scores_of(enc, ids, gens, min_new)
+                    if need_scores:
+                        window_scores.extend((b, seek[b], float(avg[i]), float(nsp[i])) for i, b in enumerate(pending))
                     again = []
                     for i, b in enumerate(pending):
-                        fallback = skip = False
-                        if compression_ratio_threshold is not None and gens[i] and \
-                                ratio(gens[i]) > compression_ratio_threshold:
-                            fallback = True
-                        if logprob_threshold is not None and avg[i] < logprob_threshold:
-                            fallback = True
-                        if no_speech_threshold is not None and avg[i] < logprob_threshold and nsp[i] > no_speech_threshold:
-                            fallback, skip = False, True
+                        fallback, skip = judge(gens[i], avg[i] if need_scores else None, nsp[i] if need_scores else None)
                         seq = gens[i][:-1] if (gens[i] and gens[i][-1] == eos) else gens[i]
                         accepted[b] = (seq, skip)
                         do_cond[b] = bool(condition_on_prev_tokens) and temp < 0.5
@@ -1574,7 +1712,7 @@ class WhisperForConditionalGeneration(nn.Module):
 
     def _generate_seek_loop(self, input_features, attention_mask, gc, language, task, is_multilingual, prompt_ids, kwargs,
                             use_graphs, return_dict_in_generate, num_beams, fallback_args=None, return_segments=False,
-                            token_ts=None, history=None):
+                            token_ts=None, history=None, seek_slots=None):
         """Timestamp-driven multi-pass transcription: `WhisperGenerationMixin.generate` steps 5-7 (TF:745-968) with
         temperature 0 and no fallback thresholds -- every utterance keeps a `seek` position in mel frames; each pass
         decodes the next <= 30 s window of every unfinished utterance with the timestamp rules, `retrieve_segment`
@@ -1654,7 +1792,7 @@ class WhisperForConditionalGeneration(nn.Module):
                                         getattr(am, "generation_config", None), "num_assistant_tokens", None) or 5),
                                     length_penalty=1.0 if getattr(gc, "length_penalty", None) is None else gc.length_penalty,
                                     early_stopping=getattr(gc, "early_stopping", False) or False,
-                                    token_timestamps=token_ts, **(history or {}), **(fallback_args or {}))
+                                    token_timestamps=token_ts, **(history or {}), **(fallback_args or {}), **(seek_slots or {}))
         rows_out = [[tok for sg in segments[b] for tok in sg["tokens"]] for b in range(B)]
         width = max((len(r) for r in rows_out), default=0)
         seqs = torch.full((B, width), pad, dtype=torch.long, device=dev)

@@ -69,6 +69,8 @@ _SIGS = {
                                  C.c_void_p], C.c_int),
     "dw_slot_step": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int64] +
                      [C.c_void_p] * 7, C.c_int),
+    "dw_slot_step_scores": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
+                            [C.c_void_p, C.c_int64] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p], C.c_int),
     "dw_logmel": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                    C.c_void_p], C.c_int),
     "dw_gemm_bf16": ([C.POINTER(DwGemm), C.c_void_p], C.c_int),
@@ -478,11 +480,17 @@ class HipOps:
         self._t1(e0, "decode_token_rows", 0.0)
 
     def slot_step(self, logits, V, tokens, length, plen, budget, done, row_t, cur, *, suppress=None, begin_suppress=None, ts_begin=-1,
-                  max_initial=-1, eos=-1, min_new=0):
+                  max_initial=-1, eos=-1, min_new=0, lp_sum=None, nsp=None, nsp_pos=None, nsp_col=-1):
         """The token selection of continuous batching for every slot in one launch (dw_slot_step, csrc/slots.hip): logits bf16
         [S, ld]; tokens int64 [S, max_len]; length / plen / budget / row_t int32 [S]; done bool [S]; cur int64 [S, 1]; all
-        updated in place on the device."""
+        updated in place on the device.  With `lp_sum` (f32 [S]) the launch is dw_slot_step_scores: it adds every generated
+        token's log-probability to lp_sum and, with nsp_col >= 0, writes softmax(row)[nsp_col] of the row behind input position
+        nsp_pos[b] (int32 [S]) into nsp (f32 [S])."""
         S = tokens.shape[0]
+        if lp_sum is not None:
+            for a, dt in ((lp_sum, torch.float32), (nsp, torch.float32), (nsp_pos, torch.int32)):
+                assert a is None or (a.dtype == dt and a.is_contiguous() and a.numel() >= S and a.device == self.device)
+            assert int(nsp_col) < int(V) and (int(nsp_col) < 0 or (nsp is not None and nsp_pos is not None))
         assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and logits.shape[0] >= S
         assert tokens.dtype == torch.int64 and tokens.is_contiguous() and cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() >= S
         for m in (suppress, begin_suppress):
@@ -490,6 +498,12 @@ class HipOps:
         for a in (length, plen, budget, row_t):
             assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() >= S
         assert done.dtype == torch.bool and done.is_contiguous() and done.numel() >= S
+        if lp_sum is not None:
+            self._chk(self.lib.dw_slot_step_scores(
+                _p(logits), S, int(V), logits.stride(0), _p(suppress), _p(begin_suppress), int(ts_begin), int(max_initial), int(eos),
+                int(min_new), _p(tokens), tokens.stride(0), _p(length), _p(plen), _p(budget), _p(done), _p(row_t), _p(cur), _p(lp_sum),
+                _p(nsp), _p(nsp_pos), int(nsp_col), self._stream()), "slot_step_scores")
+            return
         self._chk(self.lib.dw_slot_step(_p(logits), S, int(V), logits.stride(0), _p(suppress), _p(begin_suppress), int(ts_begin),
                                         int(max_initial), int(eos), int(min_new), _p(tokens), tokens.stride(0), _p(length), _p(plen),
                                         _p(budget), _p(done), _p(row_t), _p(cur), self._stream()), "slot_step")

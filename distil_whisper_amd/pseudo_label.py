@@ -47,7 +47,7 @@ class PseudoLabeller:
                  timestamp_rules=None, use_graphs=None, rank=0, world=1, suppress_tokens=None,
                  begin_suppress_tokens=None, num_beams=1, overlap=False, decode_cus=64, repetition_penalty=None,
                  no_repeat_ngram_size=0, sequence_bias=None, bad_words_ids=None, assistant_model=None, num_assistant_tokens=5,
-                 continuous=False, check_every=8, cross_kv_dtype=None):
+                 continuous=False, check_every=8, cross_kv_dtype=None, seek_slots=False, seek_group=8):
         from .longform import history_soft, refuse_continuous
         from .kv_quant import normalize_dtype
         self.model, self.fe = model, feature_extractor
@@ -55,8 +55,30 @@ class PseudoLabeller:
         # bytes the token step streams; opt-in, the labels may differ where two logits are close.  Only the token step reads
         # such a cache: the seek loop, beams and an assistant are refused here.
         cross_kv_dtype = normalize_dtype(cross_kv_dtype)
+        # seek_slots=True (with timestamp_rules): the seek loop's windows as jobs of `batch_size` slots (model.seek_decode `slots`),
+        # called over groups of seek_group * batch_size packs -- a pack's second window takes a slot as soon as the first has
+        # ended, the token steps replay from a graph, and the FP8 cross-attention K/V are allowed.  Same labels.
+        self.seek_slots, self.seek_group = bool(seek_slots), int(seek_group)
+        if self.seek_slots:
+            if timestamp_rules is None:
+                raise ValueError("PseudoLabeller(seek_slots=True) schedules the timestamp seek loop: it needs timestamp_rules")
+            if self.seek_group < 1 or int(check_every) < 1 or int(batch_size) < 1:
+                raise ValueError("PseudoLabeller(seek_slots=True) needs seek_group >= 1, check_every >= 1 and batch_size >= 1")
+            if overlap:
+                raise ValueError("PseudoLabeller(seek_slots=True) cannot be combined with overlap=True (the slot schedule "
+                                 "encodes and decodes in its own order)")
+            for on, what in ((int(num_beams) > 1, "num_beams > 1"), (assistant_model is not None, "an assistant_model"),
+                             (repetition_penalty not in (None, 1.0) or bool(no_repeat_ngram_size) or sequence_bias is not None
+                              or bad_words_ids is not None,
+                              "repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids")):
+                if on:
+                    raise NotImplementedError(f"PseudoLabeller(seek_slots=True) with {what} is not implemented on the MI355X "
+                                              "path (the slot step decodes greedily)")
+        self._seek_kw = dict(slots=int(batch_size), check_every=int(check_every), cross_kv_dtype=cross_kv_dtype,
+                             use_graphs=use_graphs) if self.seek_slots else {}
         if cross_kv_dtype is not None:
-            for on, what in ((int(num_beams) > 1, "num_beams > 1"), (timestamp_rules is not None, "timestamp_rules (the seek loop)"),
+            for on, what in ((int(num_beams) > 1, "num_beams > 1"),
+                             (timestamp_rules is not None and not self.seek_slots, "timestamp_rules (the seek loop)"),
                              (assistant_model is not None, "an assistant_model")):
                 if on:
                     raise NotImplementedError(f'PseudoLabeller(cross_kv_dtype="fp8") with {what} is not implemented on the MI355X '
@@ -111,9 +133,11 @@ class PseudoLabeller:
             self.slot_decoder = SlotDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id,
                                             suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
                                             use_graphs=use_graphs, check_every=check_every, cross_kv_dtype=cross_kv_dtype)
-        self.decoder = GreedyDecoder(model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id,
-                                     suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                                     use_graphs=use_graphs, timestamp_rules=timestamp_rules, soft=soft, cross_kv_dtype=cross_kv_dtype)
+        # (seek_slots=True decodes every window on model.seek_decode's slot decoder: no batch decoder is built)
+        self.decoder = None if self.seek_slots else GreedyDecoder(
+            model.engine, self.B, len(self.prompt) + self.max_new, eos_token_id=eos_token_id, suppress_tokens=suppress_tokens,
+            begin_suppress_tokens=begin_suppress_tokens, use_graphs=use_graphs, timestamp_rules=timestamp_rules, soft=soft,
+            cross_kv_dtype=cross_kv_dtype)
         self._wave = torch.zeros((self.B, feature_extractor.n_samples), dtype=torch.float32, device=dev)
         # overlap=True: the encoder of the next batch of packs beside the token loop of the current one (longform.two_stage_pipeline;
         # plain greedy decoding only -- the seek loop and beam search encode / decode in their own order)
@@ -172,6 +196,19 @@ class PseudoLabeller:
                     if self.eos is not None and self.eos in row:
                         row = row[:row.index(self.eos)]
                     out[pi] = [int(x) for x in row]
+            batches = []
+        if self.seek_slots:
+            # groups of seek_group * batch_size packs: the features of a group are held, its windows are scheduled on the slots
+            step = self.seek_group * self.B
+            for g0 in range(0, len(mine), step):
+                group_ = mine[g0:g0 + step]
+                feats = torch.cat([wave_to_features(group_[b0:b0 + self.B])[:len(group_[b0:b0 + self.B])].clone()
+                                   for b0 in range(0, len(group_), self.B)], 0)
+                segs = model.seek_decode(feats, [feats.shape[-1]] * len(group_), [self.prompt.tolist()] * len(group_),
+                                         lambda P: (self.max_new, 0), self.eos, self.eos, self._ts_rules["no_timestamps_token_id"],
+                                         self._ts_rules.get("max_initial_timestamp_index"), **self._beam_kw, **self._seek_kw)
+                for r, pi in enumerate(group_):
+                    out[pi] = [int(t) for sg in segs[r] for t in sg["tokens"]]
             batches = []
         for batch in batches:
             feats = wave_to_features(batch)

@@ -605,6 +605,21 @@ int dw_decode_token_rows(const DwDecodeStep* d, const int32_t* row_t, int32_t ma
 int dw_slot_step(const void* logits, int S, int V, int64_t ld, const uint8_t* suppress, const uint8_t* begin_suppress, int ts_begin,
                  int max_initial, int eos, int min_new, int64_t* tokens, int64_t tok_ld, int32_t* len, const int32_t* plen,
                  const int32_t* budget, uint8_t* done, int32_t* row_t, int64_t* cur, void* stream);
+/* dw_slot_step_scores: dw_slot_step -- the same tokens and state, launch for launch -- which also keeps the two numbers the seek
+ * loop's thresholds judge a window by.  lp_sum, nsp float [S]; nsp_pos int32 [S]; nsp_col: a column (< 0: nsp and nsp_pos are not
+ * touched and may be null).  With n = len[b] before the step and row = the slot's logits row:
+ *   done[b]                 neither number is touched
+ *   a generated step        s = the processed row the pick judges: a column the rules exclude is -inf, and so is every text
+ *                           column (c < ts_begin) when the timestamps' mass has taken the pick.
+ *                           lp_sum[b] += s[nxt] - logsumexp(s), in fp32, an EOS included (no allowed column: nothing is added)
+ *   n - 1 == nsp_pos[b]     nsp[b] = softmax(raw row)[nsp_col] when the step is forced (n < plen[b]), softmax(s)[nsp_col] when
+ *                           it is generated.  No other forced step reads its logits.
+ * The caller zeroes lp_sum[b] / nsp[b] when it fills a slot.  DW_EINVAL: as dw_slot_step; a null or misaligned lp_sum; nsp_col
+ * >= V; nsp_col >= 0 with a null or misaligned nsp / nsp_pos.  A refused call launches nothing.  One launch. */
+int dw_slot_step_scores(const void* logits, int S, int V, int64_t ld, const uint8_t* suppress, const uint8_t* begin_suppress,
+                        int ts_begin, int max_initial, int eos, int min_new, int64_t* tokens, int64_t tok_ld, int32_t* len,
+                        const int32_t* plen, const int32_t* budget, uint8_t* done, int32_t* row_t, int64_t* cur, float* lp_sum,
+                        float* nsp, const int32_t* nsp_pos, int nsp_col, void* stream);
 
 /* ---- token-level timestamps (TF:generation_whisper.py:241-381 `_extract_token_timestamps`, :43-61 `_median_filter`, :64-115
  * `_dynamic_time_warping`; reached from `generate(return_token_timestamps=True)`, TF:1146-1157).  The reference collects every
