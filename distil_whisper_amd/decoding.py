@@ -286,6 +286,27 @@ def processed_scores(scores, hist, n, *, begin_index, eos=None, no_eos=False, fi
     return sc
 
 
+def greedy_no_cache(engine, V, enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress):
+    """Greedy search that re-decodes the whole prefix at every step (no KV cache): the cross-check of the cached
+    decoder."""
+    B, dev = ids.shape[0], ids.device
+    done = torch.zeros(B, dtype=torch.bool, device=dev)
+    sup, bsup = (token_mask(t, V, dev) for t in (suppress, begin_suppress))
+    for step in range(max_new):
+        T = ids.shape[1]
+        logits, _ = engine.decode(ids.contiguous(), enc, save=False)
+        sc = logits[: B * T, :V].view(B, T, -1)[:, -1].float()
+        nxt = processed_scores(sc, ids, T, begin_index=T - step, eos=eos, no_eos=step < min_new, first=step == 0, suppress=sup,
+                               begin_suppress=bsup).argmax(-1)
+        if eos is not None:
+            nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
+            done |= nxt == eos
+        ids = torch.cat([ids, nxt[:, None]], 1)
+        if eos is not None and bool(done.all()):
+            break
+    return ids
+
+
 class GreedyDecoder:
     def __init__(self, engine, batch, max_len, eos_token_id=None, suppress_tokens=None, begin_suppress_tokens=None,
                  use_graphs=None, check_every=16, timestamp_rules=None, pad_token_id=None, soft=None, cross_kv_dtype=None):

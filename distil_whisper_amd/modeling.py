@@ -870,184 +870,34 @@ class WhisperForConditionalGeneration(nn.Module):
         Returns what the reference returns: the generated tokens only (decoder prompt and EOS stripped, right-padded
         with pad_token_id), or with `return_dict_in_generate=True` / `force_unique_generate_call=True` the full
         sequences (prompt + generated, as GenerationMixin emits them)."""
+        from . import decoding
         from . import generation as G
+        from . import seek
         self._sync_shadow()
         eng, d = self.engine, self.dims
-        # ---- arguments the engine path does not implement: loud, never ignored
-        for name, val in (("logits_processor", logits_processor), ("stopping_criteria", stopping_criteria),
-                          ("prefix_allowed_tokens_fn", prefix_allowed_tokens_fn), ("monitor_progress", monitor_progress)):
-            if val is not None and (not hasattr(val, "__len__") or len(val) > 0):
-                raise NotImplementedError(f"generate({name}=...) is not implemented on the MI355X engine path")
-        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
-        fallback_args = dict(temperatures=temps, compression_ratio_threshold=compression_ratio_threshold,
-                             logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold,
-                             condition_on_prev_tokens=bool(condition_on_prev_tokens))
-        uses_fallback = bool(condition_on_prev_tokens) or compression_ratio_threshold is not None or \
-            logprob_threshold is not None or no_speech_threshold is not None or len(temps) > 1
-        # plain sampling: as in the reference's generate_with_fallback (TF:generation_whisper.py `do_sample = temperature is not
-        # None and temperature > 0.0`), a positive `temperature` IS the switch -- `do_sample=True` alone decodes greedily
-        sample_temp = float(temps[0]) if (not uses_fallback and temps[0] is not None and temps[0] > 0.0) else None
-        engine_keys = ("encoder_outputs", "assistant_model", "decoder_input_ids", "use_cache", "assistant_per_row")
-        unknown = [k for k in kwargs if k not in G._CONFIG_KEYS and k not in engine_keys]
-        if unknown:
-            raise ValueError(f"The following `model_kwargs` are not used by the model: {unknown} (note: typos in the "
-                             "generate arguments will also show up in this list)")
-        gc = G.GenerationConfig.from_any(generation_config if generation_config is not None else self.generation_config)
-        for k in G._CONFIG_KEYS:
-            if k in kwargs and kwargs[k] is not None:
-                setattr(gc, k, kwargs[k])
-        num_beams = int(getattr(gc, "num_beams", 1) or 1)
-        if num_beams > 1 and (getattr(gc, "num_beam_groups", 1) or 1) != 1:
-            raise NotImplementedError("group beam search is not implemented on the MI355X path")
-        # ---- seek_slots=N: the timestamp seek loop as a slot schedule (seek_decode `slots`); everything it does not run is
-        # refused here, before the encoder runs
-        if seek_slots is not None:
-            rt_ = return_timestamps if return_timestamps is not None else bool(getattr(gc, "return_timestamps", False))
-            if not rt_ or force_unique_generate_call or kwargs.get("encoder_outputs") is not None:
-                raise ValueError("seek_slots schedules the timestamp seek loop: it needs return_timestamps=True and input_features "
-                                 "(not force_unique_generate_call or encoder_outputs)")
-            if isinstance(seek_slots, bool) or int(seek_slots) < 1:
-                raise ValueError("seek_slots is the number of slots, at least 1")
-            for on, combo in ((any(t is not None and float(t) > 0.0 for t in temps), "a positive temperature"),
-                              (bool(condition_on_prev_tokens), "condition_on_prev_tokens"),
-                              (num_beams > 1, "beam search (num_beams > 1)"),
-                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
-                              (bool(return_token_timestamps), "return_token_timestamps"),
-                              (getattr(gc, "repetition_penalty", None) not in (None, 1.0) or
-                               bool(int(getattr(gc, "no_repeat_ngram_size", 0) or 0)) or
-                               getattr(gc, "sequence_bias", None) is not None or getattr(gc, "bad_words_ids", None) is not None,
-                               "repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids"),
-                              (kwargs.get("use_cache", True) is False, "use_cache=False"),
-                              (bool(getattr(gc, "output_scores", False)) or bool(getattr(gc, "output_logits", False)),
-                               "output_scores / output_logits"),
-                              (kwargs.get("decoder_input_ids") is not None, "decoder_input_ids")):
-                if on:
-                    raise NotImplementedError(f"seek_slots combined with {combo} is not implemented on the MI355X path (the slot "
-                                              "step decodes the seek loop's windows greedily at temperature 0)")
-        if (getattr(gc, "num_return_sequences", 1) or 1) != 1:
-            raise NotImplementedError("num_return_sequences > 1 is not implemented on the MI355X path")
-        if num_beams == 1 and getattr(gc, "length_penalty", None) not in (None, 1.0):
-            raise NotImplementedError("length_penalty without beam search is not implemented on the MI355X path")
-        # ---- assistant_per_row=True: speculative decoding in which every row accepts its own draft prefix (decoding.
-        # assisted_greedy_decode per_row).  Single-window greedy decoding on the KV caches only; refused before anything is decoded
-        per_row = bool(kwargs.get("assistant_per_row", False))
-        if per_row:
-            if kwargs.get("assistant_model") is None:
-                raise ValueError("assistant_per_row=True needs an assistant_model")
-            if kwargs.get("use_cache", True) is False:
-                raise NotImplementedError("assistant_per_row=True runs on the KV caches (not with use_cache=False)")
-            if num_beams > 1:
-                raise NotImplementedError("assistant_per_row=True cannot be combined with beam search")
-        # history-dependent processors / sampling (GenerationMixin's repetition penalty, no-repeat n-gram, temperature / top-k /
-        # top-p sampling): on the single-call KV-cache decoder (decoding.GreedyDecoder `soft`); elsewhere they raise below
-        soft = None
-        rp, nrn = getattr(gc, "repetition_penalty", None), int(getattr(gc, "no_repeat_ngram_size", 0) or 0)
-        # sequence_bias / bad_words_ids (SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor): validated and flattened on the
-        # host, applied by the selection kernel of greedy decoding (decoding.GreedyDecoder `soft`); elsewhere they raise
-        bias_table = None
-        if getattr(gc, "sequence_bias", None) is not None or getattr(gc, "bad_words_ids", None) is not None:
-            from .decoding import sequence_bias_table
-            bias_table = sequence_bias_table(getattr(gc, "sequence_bias", None), getattr(gc, "bad_words_ids", None), d.vocab,
-                                             gc.eos_token_id)
-        if bias_table is not None:
-            n_utt = (input_features if input_features is not None else kwargs.get("encoder_outputs"))
-            n_utt = n_utt.shape[0] if torch.is_tensor(n_utt) and n_utt.dim() == 3 else None
-            for on, combo in ((num_beams > 1, "beam search (num_beams > 1)"),
-                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
-                              (sample_temp is not None, "plain sampling (a positive temperature)"),
-                              (kwargs.get("use_cache", True) is False, "use_cache=False"),
-                              (bool(return_dict_in_generate or getattr(gc, "return_dict_in_generate", False)) and
-                               (bool(getattr(gc, "output_scores", False)) or bool(getattr(gc, "output_logits", False))),
-                               "output_scores / output_logits"),
-                              (bool(return_token_timestamps), "return_token_timestamps"),
-                              (bool(condition_on_prev_tokens) and n_utt is not None and n_utt > 1,
-                               "condition_on_prev_tokens=True over several utterances (the reference left-pads that batch with "
-                               "pad_token_id and its processors count the pads as history; pass one utterance per call)")):
-                if on:
-                    raise NotImplementedError(f"sequence_bias / bad_words_ids combined with {combo} are not implemented on the "
-                                              "MI355X path (they are applied by the selection kernel of greedy decoding)")
-        if sample_temp is not None or rp not in (None, 1.0) or nrn or bias_table is not None:
-            # (an unset top_k is GenerationMixin's global default of 50 when sampling; run_eval.py:739 passes top_k=0 = off)
-            tk = getattr(gc, "top_k", None)
-            soft = dict(do_sample=sample_temp is not None, temperature=sample_temp, top_k=50 if tk is None else tk,
-                        top_p=getattr(gc, "top_p", None), repetition_penalty=rp, no_repeat_ngram_size=nrn)
-            if bias_table is not None:
-                soft["sequence_bias"] = bias_table
-            if num_beams > 1 or kwargs.get("assistant_model") is not None or kwargs.get("use_cache", True) is False:
-                raise NotImplementedError("sampling / repetition_penalty / no_repeat_ngram_size are implemented for greedy "
-                                          "single-window decoding with the KV cache (not with beams, an assistant or use_cache=False)")
-        if gc.decoder_start_token_id is None:
-            gc.decoder_start_token_id = d.decoder_start_token_id
-        # ---- per-step scores (TF:generation/utils.py `_sample`: `scores` / `raw_logits`); without return_dict_in_generate the
-        # reference drops both flags, and so does this path
-        as_dict = bool(return_dict_in_generate or getattr(gc, "return_dict_in_generate", False))
-        want_scores = as_dict and bool(getattr(gc, "output_scores", False))
-        want_logits = as_dict and bool(getattr(gc, "output_logits", False))
-        if want_scores or want_logits:
-            what = " / ".join(n for n, w in (("output_scores", want_scores), ("output_logits", want_logits)) if w)
-            for on, combo in ((num_beams > 1, "beam search (num_beams > 1)"),
-                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
-                              (soft is not None, "sampling / repetition_penalty / no_repeat_ngram_size")):
-                if on:
-                    raise NotImplementedError(f"{what} combined with {combo} is not implemented on the MI355X path (per-step "
-                                              "scores come from single-window greedy search)")
-        # ---- token-level timestamps (TF:1685-1700 `_set_num_frames`): what the alignment pass needs, or a loud refusal
-        token_ts = None
-        if return_token_timestamps:
-            from . import alignment as A
-            if task == "translate" or (task is None and getattr(gc, "task", None) == "translate"):
-                A.logger.warning(A.TRANSLATE_WARNING)
-            if not hasattr(gc, "alignment_heads"):
-                raise A.TokenTimestampsUnavailable(A.NO_ALIGNMENT_HEADS)
-            A.check_filter_width(int(d.median_filter_width))
-            if num_beams > 1 or kwargs.get("assistant_model") is not None or sample_temp is not None or uses_fallback:
-                raise NotImplementedError(
-                    "return_token_timestamps is implemented for greedy decoding (single window and the timestamp seek loop); "
-                    "combined with beam search, an assistant_model, sampling or the temperature-fallback / "
-                    "condition_on_prev_tokens heuristics it is not implemented on the MI355X path")
-            if attention_mask is not None:
-                nf = [int(x) for x in attention_mask.sum(-1).tolist()]
-            else:
-                A.warn_once(A.NO_ATTENTION_MASK)
-                nf = None
-            token_ts = dict(alignment_heads=[list(x) for x in gc.alignment_heads], num_frames=nf,
-                            time_precision=time_precision)
-        # ---- FP8 cross-attention K/V: only the token step of decoding.GreedyDecoder reads them; refused before the encoder runs
-        from . import kv_quant
-        cross_kv_dtype = kv_quant.normalize_dtype(cross_kv_dtype)
-        if cross_kv_dtype is not None:
-            kv_quant.check_width(d.d_model)
-            if kwargs.get("use_cache", True) is False:
-                raise ValueError('cross_kv_dtype="fp8" is a format of the KV cache (not with use_cache=False)')
-            for on, combo in ((num_beams > 1, "beam search (num_beams > 1)"),
-                              (kwargs.get("assistant_model") is not None, "an assistant_model"),
-                              (want_scores or want_logits, "output_scores / output_logits"),
-                              (bool(return_token_timestamps), "return_token_timestamps"),
-                              (uses_fallback and seek_slots is None,
-                               "the temperature fallback / condition_on_prev_tokens (the seek loop)")):
-                if on:
-                    raise NotImplementedError(f'cross_kv_dtype="fp8" combined with {combo} is not implemented on the MI355X path '
-                                              "(only the token step reads FP8 cross-attention K/V)")
+        # ---- every argument resolved once; what the engine path does not run is refused here (generation.REFUSALS)
+        p = G.resolve_generate(
+            d, generation_config if generation_config is not None else self.generation_config, kwargs,
+            input_features=input_features, return_timestamps=return_timestamps, task=task, temperature=temperature,
+            unimplemented=dict(logits_processor=logits_processor, stopping_criteria=stopping_criteria,
+                               prefix_allowed_tokens_fn=prefix_allowed_tokens_fn, monitor_progress=monitor_progress),
+            condition_on_prev_tokens=condition_on_prev_tokens, compression_ratio_threshold=compression_ratio_threshold,
+            logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold, attention_mask=attention_mask,
+            time_precision=time_precision, return_token_timestamps=return_token_timestamps, return_segments=return_segments,
+            return_dict_in_generate=return_dict_in_generate, force_unique_generate_call=force_unique_generate_call,
+            use_graphs=use_graphs, cross_kv_dtype=cross_kv_dtype, seek_slots=seek_slots)
+        gc, num_beams = p.gc, p.num_beams
         # ---- encoder
         encoder_outputs = kwargs.get("encoder_outputs")
         if encoder_outputs is not None:
-            if uses_fallback:
-                raise NotImplementedError("temperature fallback / condition_on_prev_tokens need input_features (the seek "
-                                          "loop encodes every window itself)")
-            enc = encoder_outputs
-            if not torch.is_tensor(enc):
-                enc = enc.last_hidden_state if hasattr(enc, "last_hidden_state") else enc[0]
-            B = enc.shape[0] if enc.dim() == 3 else enc.shape[0] // d.max_src
-            if enc.numel() != B * d.max_src * d.d_model:
-                raise ValueError(f"encoder_outputs must cover {d.max_src} positions of width {d.d_model} per row")
-            enc = enc.reshape(-1, d.d_model).to(eng.lowp).contiguous()   # the dtype `encode` returns (GEMM operand)
+            G.refuse(p, "encoder_outputs")
+            enc, B = self._given_encoder_output(encoder_outputs)
             dev = enc.device
         else:
             if input_features is None:
                 raise ValueError("input_features or encoder_outputs are required")
             frames = input_features.shape[-1]
-            rt = return_timestamps if return_timestamps is not None else bool(getattr(gc, "return_timestamps", False))
-            if frames > 2 * d.max_src and not rt:
+            if frames > 2 * d.max_src and not p.return_timestamps:
                 raise ValueError(
                     "You have passed more than 3000 mel input features (> 30 seconds) which automatically enables "
                     "long-form generation which requires the model to predict timestamp tokens. Please either pass "
@@ -1056,61 +906,32 @@ class WhisperForConditionalGeneration(nn.Module):
                 if prompt_condition_type not in ("first-segment", "all-segments"):
                     raise ValueError("`prompt_condition_type` must be either 'first-segment' or 'all-segments'")
                 gc.prompt_condition_type = prompt_condition_type
-            if frames > 2 * d.max_src or (rt and not force_unique_generate_call):
+            if frames > 2 * d.max_src or (p.return_timestamps and not force_unique_generate_call):
                 # the reference's seek loop (TF:784-903): with timestamps every window is decoded until its audio is
                 # consumed, also when the input is a single 30 s window (run_pseudo_labelling.py:861-996 calls it so)
-                if cross_kv_dtype is not None and seek_slots is None:
-                    raise NotImplementedError('cross_kv_dtype="fp8" is implemented for single-window decoding, not inside the '
-                                              "timestamp seek loop (return_timestamps=True without force_unique_generate_call, or "
-                                              "more than 30 s of input), on the MI355X path")
-                if sample_temp is not None:
-                    raise NotImplementedError("sampling (a positive temperature as a plain switch) is implemented for "
-                                              "single-window decoding, not inside the timestamp seek loop, on the MI355X path "
-                                              "(a temperature tuple runs the seek loop's sampled fallback passes)")
-                if per_row:
-                    raise NotImplementedError("assistant_per_row=True is implemented for single-window decoding, not inside the "
-                                              "timestamp seek loop (return_timestamps=True without force_unique_generate_call, or "
-                                              "more than 30 s of input), on the MI355X path")
-                if want_scores or want_logits:
-                    raise NotImplementedError("output_scores / output_logits inside the timestamp seek loop (return_timestamps=True "
-                                              "without force_unique_generate_call, or more than 30 s of input) are not implemented "
-                                              "on the MI355X path")
-                return self._generate_seek_loop(input_features, attention_mask, gc, language, task, is_multilingual,
-                                                prompt_ids, kwargs, use_graphs, return_dict_in_generate, num_beams,
-                                                fallback_args, return_segments, token_ts,
-                                                history=dict(repetition_penalty=rp, no_repeat_ngram_size=nrn,
-                                                             sequence_bias=bias_table),
-                                                seek_slots=None if seek_slots is None else dict(
-                                                    slots=int(seek_slots), cross_kv_dtype=cross_kv_dtype, use_graphs=use_graphs))
-            if return_segments:
-                raise NotImplementedError("return_segments comes with the timestamp seek loop (return_timestamps=True) "
-                                          "on the MI355X path")
-            if uses_fallback:
-                raise NotImplementedError("temperature fallback / condition_on_prev_tokens are implemented for the "
-                                          "timestamp seek loop (return_timestamps=True) only on the MI355X path")
+                p.seek_loop = True
+                p.all_segments = getattr(gc, "prompt_condition_type", "first-segment") == "all-segments"
+                G.refuse(p, "seek_loop", "all_segments", "assistant")
+                return seek.generate_seek_loop(self, p, input_features, attention_mask, language, task, is_multilingual,
+                                               prompt_ids, kwargs, return_segments)
+            p.single_window = True
+            G.refuse(p, "single_window")
             if frames != 2 * d.max_src:
                 raise ValueError(f"Whisper expects the mel input features to be of length {2 * d.max_src}, but found "
                                  f"{frames}. Make sure to pad the input mel features to {2 * d.max_src}.")
-            B = input_features.shape[0]
-            dev = input_features.device
+            B, dev = input_features.shape[0], input_features.device
             enc, _ = eng.encode(input_features.to(torch.float32).contiguous(), save=False)
         # ---- decoder prompt (TF:1384-1608, 1853-1918)
-        if return_timestamps is None:
-            return_timestamps = bool(getattr(gc, "return_timestamps", False))
-        if return_timestamps and not hasattr(gc, "no_timestamps_token_id"):
-            raise ValueError("You are trying to return timestamps, but the generation config is not properly set. Make "
-                             "sure to initialize the generation config with the correct attributes that are needed "
-                             "such as `no_timestamps_token_id`.")
-        gc.return_timestamps = bool(return_timestamps)
+        if p.return_timestamps and not hasattr(gc, "no_timestamps_token_id"):
+            raise ValueError(G.NO_TIMESTAMPS_TOKEN)
+        gc.return_timestamps = bool(p.return_timestamps)
         G.set_language_and_task(gc, language, task, is_multilingual)
         if prompt_condition_type is not None and prompt_condition_type not in ("first-segment", "all-segments"):
             raise ValueError("`prompt_condition_type` must be either 'first-segment' or 'all-segments'")
-        if "decoder_input_ids" in kwargs and kwargs["decoder_input_ids"] is not None:
+        if kwargs.get("decoder_input_ids") is not None:
             ids = kwargs["decoder_input_ids"].to(dev).long().clone()
         else:
-            def detect():
-                return self._detect_language(enc, B, gc)
-            rows = G.retrieve_init_tokens(gc, B, detect)
+            rows = G.retrieve_init_tokens(gc, B, lambda: self._detect_language(enc, B, gc))
             ids = torch.as_tensor(rows, dtype=torch.long, device=dev)
             if prompt_ids is not None:
                 pr = torch.as_tensor(prompt_ids, dtype=torch.long, device=dev).reshape(-1)
@@ -1126,107 +947,109 @@ class WhisperForConditionalGeneration(nn.Module):
             pad = eos
         suppress = list(gc.suppress_tokens) if gc.suppress_tokens else None
         begin_suppress = list(gc.begin_suppress_tokens) if gc.begin_suppress_tokens else None
-        assistant_model = kwargs.get("assistant_model")
-        use_cache = kwargs.get("use_cache", True)
-        if use_cache is None:
-            use_cache = True
-        if use_graphs is None:
-            use_graphs = False
+        assistant_model, use_graphs = p.assistant_model, bool(use_graphs)
+        ts_rules = None                        # (single window with timestamps: force_unique_generate_call)
+        if gc.return_timestamps:
+            ts_rules = G.timestamp_rules(gc.no_timestamps_token_id, getattr(gc, "max_initial_timestamp_index", None), begin_index=P)
+        if ts_rules is not None and eos is None and num_beams == 1 and (assistant_model is not None or p.use_cache):
+            raise ValueError("return_timestamps=True needs eos_token_id in the generation config")
+        # ---- one of four token loops
         if num_beams > 1:
             # beam search (run_eval.py:143, 693; run_distillation.py:1428-1436): TF `_beam_search` on the KV-cache decoder
-            from .decoding import beam_search_decode
-            if assistant_model is not None:
-                raise ValueError("assistant_model cannot be combined with beam search (TF raises the same)")
+            G.refuse(p, "assistant")
             if eos is None:
                 raise ValueError("beam search needs eos_token_id in the generation config")
-            ts_rules = None
-            if gc.return_timestamps:
-                ts_rules = dict(begin_index=P, no_timestamps_token_id=int(gc.no_timestamps_token_id),
-                                max_initial_timestamp_index=getattr(gc, "max_initial_timestamp_index", None))
             lp = getattr(gc, "length_penalty", None)
             es = getattr(gc, "early_stopping", False)
-            seqs = beam_search_decode(eng, enc, ids, max_new, num_beams, eos, pad_token_id=pad, suppress_tokens=suppress,
-                                      begin_suppress_tokens=begin_suppress, min_new_tokens=min_new,
-                                      length_penalty=1.0 if lp is None else float(lp),
-                                      early_stopping=False if es is None else es, timestamp_rules=ts_rules)
+            seqs = decoding.beam_search_decode(eng, enc, ids, max_new, num_beams, eos, pad_token_id=pad, suppress_tokens=suppress,
+                                               begin_suppress_tokens=begin_suppress, min_new_tokens=min_new,
+                                               length_penalty=1.0 if lp is None else float(lp),
+                                               early_stopping=False if es is None else es, timestamp_rules=ts_rules)
         elif assistant_model is not None:
-            # speculative decoding (run_eval.py:578-599, 706-707): the assistant drafts, this model verifies.  An
-            # assistant with this model's encoder dimensions re-uses the encoder output (the distilled student keeps
-            # a frozen copy of the teacher's encoder); otherwise it encodes the features itself.
-            from .decoding import assisted_greedy_decode
-            a_ts_rules = None
-            if gc.return_timestamps:       # (single window, force_unique_generate_call: the seek loop has its own branch)
-                if eos is None:
-                    raise ValueError("return_timestamps=True needs eos_token_id in the generation config")
-                a_ts_rules = dict(begin_index=P, no_timestamps_token_id=int(gc.no_timestamps_token_id),
-                                  max_initial_timestamp_index=getattr(gc, "max_initial_timestamp_index", None))
             begin_suppress = None          # TF:719-721: the model must be able to return EOS right away
-            assistant_model._sync_shadow()
-            ad = assistant_model.dims
-            if _assistant_shares_encoder(assistant_model, d) or \
-                    (input_features is None and ad.d_model == d.d_model):
-                enc_a = enc.to(assistant_model.engine.lowp)
-            else:
-                if input_features is None:
-                    raise ValueError("the assistant needs input_features (its encoder differs from this model's)")
-                enc_a, _ = assistant_model.engine.encode(input_features.to(torch.float32).contiguous(), save=False)
-            k = getattr(gc, "num_assistant_tokens", None) or \
-                getattr(getattr(assistant_model, "generation_config", None), "num_assistant_tokens", None) or 5
-            seqs, self.last_drafted, self.last_accepted = assisted_greedy_decode(
-                eng, assistant_model.engine, enc, enc_a, ids, max_new, int(k), eos, suppress_tokens=suppress,
-                min_new_tokens=min_new, pad_token_id=pad, timestamp_rules=a_ts_rules, per_row=per_row)
-        elif use_cache:
-            from .decoding import GreedyDecoder
-            ts_rules = None
-            if gc.return_timestamps:
-                if eos is None:
-                    raise ValueError("return_timestamps=True needs eos_token_id in the generation config")
-                ts_rules = dict(begin_index=P, no_timestamps_token_id=int(gc.no_timestamps_token_id),
-                                max_initial_timestamp_index=getattr(gc, "max_initial_timestamp_index", None))
-            total = P + max_new
-            key = (B, total, eos, pad, bool(use_graphs), tuple(suppress or ()), tuple(begin_suppress or ()),
-                   None if ts_rules is None else tuple(sorted(ts_rules.items())),
-                   None if soft is None else tuple(sorted((k, v) for k, v in soft.items())), cross_kv_dtype)
-            dec = self._decoders.get(key)
-            if dec is None:
-                dec = GreedyDecoder(eng, B, total, eos_token_id=eos, suppress_tokens=suppress,
-                                    begin_suppress_tokens=begin_suppress, use_graphs=use_graphs,
-                                    check_every=16 if use_graphs else 1, timestamp_rules=ts_rules, pad_token_id=pad, soft=soft,
-                                    cross_kv_dtype=cross_kv_dtype)
-                self._decoders = {key: dec}        # one live decoder (its graphs pin the K/V cache buffers)
-            seqs = dec.run(enc, ids, max_new, min_new)
+            seqs = self._assisted_decode(p, enc, ids, input_features, max_new, min_new, eos, pad, suppress, ts_rules)
+        elif p.use_cache:
+            seqs = self._cached_decode(p, enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress, ts_rules, use_graphs)
         else:
             if gc.return_timestamps:
                 raise ValueError("return_timestamps=True runs on the KV-cache decoder (use_cache=True)")
-            seqs = self._greedy_no_cache(enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress)
-        seqs = self._trim_finished(seqs, P, eos, pad)
+            seqs = decoding.greedy_no_cache(eng, d.vocab, enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress)
+        seqs = G.trim_finished(seqs, P, eos, pad)
+        return self._generate_result(p, seqs, enc, P, min_new, eos, pad, suppress, begin_suppress, force_unique_generate_call)
+
+    def _given_encoder_output(self, enc):
+        """`generate(encoder_outputs=)`: a tensor, a BaseModelOutput or a tuple -> (rows in the dtype `encode` returns, B)."""
+        d = self.dims
+        if not torch.is_tensor(enc):
+            enc = enc.last_hidden_state if hasattr(enc, "last_hidden_state") else enc[0]
+        B = enc.shape[0] if enc.dim() == 3 else enc.shape[0] // d.max_src
+        if enc.numel() != B * d.max_src * d.d_model:
+            raise ValueError(f"encoder_outputs must cover {d.max_src} positions of width {d.d_model} per row")
+        return enc.reshape(-1, d.d_model).to(self.engine.lowp).contiguous(), B      # (GEMM operand)
+
+    def _cached_decode(self, p, enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress, ts_rules, use_graphs):
+        """Greedy or sampled decoding on the model's one live decoding.GreedyDecoder, rebuilt when its key changes."""
+        from .decoding import GreedyDecoder
+        B, total = ids.shape[0], ids.shape[1] + max_new
+        key = (B, total, eos, pad, use_graphs, tuple(suppress or ()), tuple(begin_suppress or ()),
+               None if ts_rules is None else tuple(sorted(ts_rules.items())),
+               None if p.soft is None else tuple(sorted((k, v) for k, v in p.soft.items())), p.cross_kv_dtype)
+        dec = self._decoders.get(key)
+        if dec is None:
+            dec = GreedyDecoder(self.engine, B, total, eos_token_id=eos, suppress_tokens=suppress,
+                                begin_suppress_tokens=begin_suppress, use_graphs=use_graphs, check_every=16 if use_graphs else 1,
+                                timestamp_rules=ts_rules, pad_token_id=pad, soft=p.soft, cross_kv_dtype=p.cross_kv_dtype)
+            self._decoders = {key: dec}        # one live decoder (its graphs pin the K/V cache buffers)
+        return dec.run(enc, ids, max_new, min_new)
+
+    def _assisted_decode(self, p, enc, ids, input_features, max_new, min_new, eos, pad, suppress, ts_rules):
+        """Speculative decoding (run_eval.py:578-599, 706-707): the assistant drafts, this model verifies.  An assistant with
+        this model's encoder dimensions re-uses the encoder output (the distilled student keeps a frozen copy of the teacher's
+        encoder); otherwise it encodes the features itself."""
+        from .decoding import assisted_greedy_decode
+        am, d, gc = p.assistant_model, self.dims, p.gc
+        am._sync_shadow()
+        if _assistant_shares_encoder(am, d) or (input_features is None and am.dims.d_model == d.d_model):
+            enc_a = enc.to(am.engine.lowp)
+        else:
+            if input_features is None:
+                raise ValueError("the assistant needs input_features (its encoder differs from this model's)")
+            enc_a, _ = am.engine.encode(input_features.to(torch.float32).contiguous(), save=False)
+        k = getattr(gc, "num_assistant_tokens", None) or \
+            getattr(getattr(am, "generation_config", None), "num_assistant_tokens", None) or 5
+        seqs, self.last_drafted, self.last_accepted = assisted_greedy_decode(
+            self.engine, am.engine, enc, enc_a, ids, max_new, int(k), eos, suppress_tokens=suppress,
+            min_new_tokens=min_new, pad_token_id=pad, timestamp_rules=ts_rules, per_row=p.per_row)
+        return seqs
+
+    def _generate_result(self, p, seqs, enc, P, min_new, eos, pad, suppress, begin_suppress, unique_call):
+        """What `generate` returns for a single window, shaped as the reference shapes it (TF:913-968)."""
+        from . import generation as G
+        gc, token_ts = p.gc, p.token_ts
         step_scores = step_logits = None
-        if want_scores or want_logits:
+        if p.want_scores or p.want_logits:
             # one teacher-forced pass over the finished sequences + csrc/score.hip (scoring.py says why a second pass)
             from .scoring import score_sequences
-            ts_rules = None
+            sc_rules = None
             if gc.return_timestamps:
-                ts_rules = dict(no_timestamps_token_id=int(gc.no_timestamps_token_id),
-                                max_initial_timestamp_index=getattr(gc, "max_initial_timestamp_index", None))
+                sc_rules = G.timestamp_rules(gc.no_timestamps_token_id, getattr(gc, "max_initial_timestamp_index", None))
             step_scores, step_logits = score_sequences(
                 self, seqs, enc, P, dict(suppress_tokens=suppress, begin_suppress_tokens=begin_suppress, min_new_tokens=min_new,
-                                         eos_token_id=eos, timestamp_rules=ts_rules), want_scores, want_logits)
+                                         eos_token_id=eos, timestamp_rules=sc_rules), p.want_scores, p.want_logits)
         if token_ts is not None:
-            # TF:1146-1157: one alignment pass over the finished sequences; which shape comes back: TF:913-968
+            # TF:1146-1157: one alignment pass over the finished sequences
             from .alignment import extract_token_timestamps
             ts = extract_token_timestamps(self, seqs, enc, token_ts["alignment_heads"], token_ts["num_frames"], P,
                                           token_ts["time_precision"])
-            if as_dict:
+            if p.as_dict:
                 return G.GenerateOutput(seqs, scores=step_scores, token_timestamps=ts, logits=step_logits)
-            if force_unique_generate_call:
+            if unique_call:
                 return {"sequences": seqs, "token_timestamps": ts}
             plain, plain_ts = G.strip_and_pad(seqs, P, eos, pad, token_timestamps=ts)
             return {"sequences": plain, "token_timestamps": plain_ts}
-        if as_dict:
+        if p.as_dict:
             return G.GenerateOutput(seqs, scores=step_scores, logits=step_logits)
-        if force_unique_generate_call:
-            return seqs
-        return G.strip_and_pad(seqs, P, eos, pad)
+        return seqs if unique_call else G.strip_and_pad(seqs, P, eos, pad)
 
     def compute_transition_scores(self, sequences, scores, beam_indices=None, normalize_logits=False):
         """`GenerationMixin.compute_transition_scores`: f32 [batch, steps], the score of every generated token of `sequences` in
@@ -1308,535 +1131,21 @@ class WhisperForConditionalGeneration(nn.Module):
             lengths.  `last_seek_stats` holds the token steps, the encoder calls' batch sizes and the most encoded windows held;
             `last_window_scores` (either loop, with a threshold) the numbers every window was judged by.
         -> per utterance the list of segments {"start", "end", "tokens"}."""
-        import math
-        import zlib
-        from . import generation as G
-        from .decoding import SAMPLE_TORCH_ENV, GreedyDecoder, processed_scores, token_mask
-        eng, d = self.engine, self.dims
-        B = input_features.shape[0]
-        if slots is None:
-            if cross_kv_dtype is not None or use_graphs is not None:
-                raise ValueError("seek_decode: cross_kv_dtype / use_graphs belong to the slot schedule (slots=N)")
-        else:
-            if int(slots) < 1 or int(check_every) < 1:
-                raise ValueError("seek_decode(slots=N) needs N >= 1 slots and check_every >= 1")
-            _t = temperatures if isinstance(temperatures, (list, tuple)) else [temperatures]
-            for on, what in ((any(x is not None and float(x) > 0.0 for x in _t), "a positive temperature (sampled fallback passes)"),
-                             (bool(condition_on_prev_tokens), "condition_on_prev_tokens"),
-                             (int(num_beams) > 1, "num_beams > 1"),
-                             (assistant is not None, "an assistant_model"),
-                             (token_timestamps is not None, "return_token_timestamps"),
-                             (repetition_penalty not in (None, 1.0) or bool(no_repeat_ngram_size) or sequence_bias is not None,
-                              "repetition_penalty / no_repeat_ngram_size / sequence_bias / bad_words_ids")):
-                if on:
-                    raise NotImplementedError(f"the timestamp seek loop on slots (seek_slots / slots=N) with {what} is not "
-                                              "implemented on the MI355X path (the slot step decodes greedily at temperature 0)")
-            if not callable(init_tokens) and len({len(r) for r in init_tokens}) > 1:
-                raise NotImplementedError("the timestamp seek loop on slots needs decoder prompts of one length (init_tokens rows "
-                                          "of different lengths)")
-        rep_pen = None if repetition_penalty in (None, 1.0) else float(repetition_penalty)
-        ngram = int(no_repeat_ngram_size or 0)
-        hist_soft = None
-        if sequence_bias is not None:
-            if int(num_beams) > 1 or assistant is not None or token_timestamps is not None:
-                raise NotImplementedError("sequence_bias / bad_words_ids inside the timestamp seek loop are implemented for greedy "
-                                          "passes (not with beams, an assistant or token timestamps) on the MI355X path")
-            if condition_on_prev_tokens and B > 1:
-                raise NotImplementedError(
-                    "sequence_bias / bad_words_ids with condition_on_prev_tokens=True and more than one utterance are not "
-                    "implemented on the MI355X path: the reference left-pads that batch with pad_token_id and its processors "
-                    "then count the pads as history, while this package decodes rows in groups of equal prompt length (no "
-                    "pads).  Pass one utterance per call")
-        if rep_pen is not None or ngram:
-            if int(num_beams) > 1 or assistant is not None:
-                raise NotImplementedError("repetition_penalty / no_repeat_ngram_size inside the timestamp seek loop are "
-                                          "implemented for greedy passes (not with beams or an assistant) on the MI355X path")
-            if condition_on_prev_tokens and B > 1:
-                raise NotImplementedError(
-                    "repetition_penalty / no_repeat_ngram_size with condition_on_prev_tokens=True and more than one utterance "
-                    "are not implemented on the MI355X path: the reference left-pads that batch with pad_token_id and its "
-                    "processors then count the pads as history, while this package decodes rows in groups of equal prompt "
-                    "length (no pads).  Pass one utterance per call")
-            hist_soft = dict(do_sample=False, repetition_penalty=rep_pen, no_repeat_ngram_size=ngram)
-        if sequence_bias is not None:
-            hist_soft = dict(hist_soft or dict(do_sample=False, repetition_penalty=rep_pen, no_repeat_ngram_size=ngram),
-                             sequence_bias=sequence_bias)
-        dev = input_features.device
-        W, V = 2 * d.max_src, d.vocab
-        feats = input_features.to(torch.float32)
-        seek = [0] * B
-        temps = [0.0 if x is None else float(x) for x in (temperatures if isinstance(temperatures, (list, tuple))
-                                                         else [temperatures])]
-
-        def window(rows):
-            seg = torch.zeros((len(rows), feats.shape[1], W), dtype=torch.float32, device=dev)
-            for i, b in enumerate(rows):
-                n = min(max_frames[b] - seek[b], W)
-                seg[i, :, :n] = feats[b, :, seek[b]:seek[b] + n]
-            return seg
-        if callable(init_tokens):
-            init = init_tokens(lambda: detect_language(eng.encode(window(list(range(B))), save=False)[0]))
-        else:
-            init = init_tokens
-        P0 = len(init[0])
-        nts = int(no_timestamps_token_id)
-        tb = nts + 1
-        cut_off = d.max_tgt // 2 - 1
-        prev_sot = prev_sot_token_id
-        if prev_sot is None and suppress_tokens is not None and len(suppress_tokens) >= 2:
-            prev_sot = suppress_tokens[-2]
-        need_scores = logprob_threshold is not None or no_speech_threshold is not None
-        if no_speech_threshold is not None and logprob_threshold is None:
-            raise ValueError("no_speech_threshold needs logprob_threshold (the reference compares both)")
-        if token_timestamps is not None and (any(t > 0.0 for t in temps) or assistant is not None or int(num_beams) > 1):
-            raise NotImplementedError("token timestamps in the seek loop are implemented for greedy passes (no sampled fallback, "
-                                      "assistant or beams) on the MI355X path")
-
-        def vmask(ids):                                # (all-false where no id names a column: the sampling kernel is given both)
-            mk = token_mask(ids, V, dev)
-            return torch.zeros(V, dtype=torch.bool, device=dev) if mk is None else mk
-        sup, bsup = vmask(suppress_tokens), vmask(begin_suppress_tokens)
-        ts_rules = dict(no_timestamps_token_id=nts, max_initial_timestamp_index=max_initial_timestamp_index)
-
-        def processed(raw, hist, n, P, min_new):
-            """The reference's processed scores of one step: raw f32 [r, V], hist int64 [r, >= n] (n tokens so far)."""
-            return processed_scores(raw, hist, n, begin_index=P, eos=eos, no_eos=n - P < min_new, first=n == P, suppress=sup,
-                                    begin_suppress=bsup, timestamp_rules=ts_rules, repetition_penalty=rep_pen, no_repeat_ngram=ngram,
-                                    sequence_bias=sequence_bias)
-
-        # the sampled passes select inside the kernel (dw_sample_select) where the ops have it: per step one `exponential_` draw
-        # of the shape [r, V] that `torch.multinomial` would draw itself, plus one launch; DW_SAMPLE_TORCH=1 keeps the torch ops
-        # (the sampling kernel takes no bias table: with one the sampled passes are the torch ops of `processed`)
-        sample_kernel = hasattr(eng.ops, "sample_select") and os.environ.get(SAMPLE_TORCH_ENV, "0") in ("", "0") and \
-            sequence_bias is None
-
-        def sample(enc, ids, max_new, min_new, temp):
-            """Multinomial sampling at temperature `temp` over the processed scores (fallback passes)."""
-            r, P = ids.shape
-            cache = eng.decode_init(enc, r, P + max_new)
-            toks = torch.full((r, P + max_new), pad, dtype=torch.long, device=dev)
-            toks[:, :P] = ids
-            done = torch.zeros(r, dtype=torch.bool, device=dev)
-            logits = eng.decode_multi(ids, cache).view(r, P, -1)[:, -1]
-            if sample_kernel:
-                noise = torch.empty((r, V), dtype=torch.float32, device=dev)
-                cur = torch.empty((r, 1), dtype=torch.long, device=dev)
-            n = P
-            while True:
-                if sample_kernel:
-                    # processors, temperature, the draw and the EOS / pad bookkeeping in one launch (stepping stays eager: r
-                    # changes from pass to pass); the generator is consumed as by the multinomial below
-                    noise.exponential_(1.0)
-                    eng.ops.sample_select(
-                        logits, V, toks, n, cur, noise, suppress=sup.view(torch.uint8), begin_suppress=bsup.view(torch.uint8),
-                        first=(n == P), no_eos=(n - P < min_new), ts_begin=tb,
-                        max_initial=-1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index),
-                        begin_index=P, eos=eos, fill=pad, done=done, repetition_penalty=1.0 if rep_pen is None else rep_pen,
-                        no_repeat_ngram=ngram, temperature=temp)
-                    nxt = cur[:, 0]
-                else:
-                    pr = torch.softmax(processed(logits[:, :V].float(), toks, n, P, min_new) / temp, -1)
-                    nxt = torch.multinomial(pr, 1)[:, 0]
-                    nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
-                    toks[:, n] = nxt
-                    done = done | (nxt == eos)
-                n += 1
-                if n >= P + max_new or bool(done.all()):
-                    break
-                logits = eng.decode_step(nxt[:, None].contiguous(), cache)
-            return toks[:, :n]
-
-        def scores_of(enc, ids, gens, min_new):
-            """(average log-probability of the chosen tokens, P(<|nospeech|>) after <|startoftranscript|>) per row from
-            ONE teacher-forced decoder pass over prompt + generated tokens (TF `_retrieve_avg_logprobs`, 1958-1975;
-            `WhisperNoSpeechDetection`, TF:generation/logits_process.py)."""
-            r, P = ids.shape
-            L = max(1, max(len(g) for g in gens))
-            full = torch.full((r, P + L), eos, dtype=torch.long, device=dev)
-            full[:, :P] = ids
-            for i, g in enumerate(gens):
-                if g:
-                    full[i, P:P + len(g)] = torch.as_tensor(g, dtype=torch.long, device=dev)
-            T = full.shape[1]
-            logits, _ = eng.decode(full[:, :T - 1].contiguous() if T > 1 else full, enc, save=False)
-            logits = logits[:r * (T - 1)].view(r, T - 1, -1)[:, :, :V].float()
-            tot = torch.zeros(r, dtype=torch.float64, device=dev)
-            first = None
-            for j in range(L):
-                sc = processed(logits[:, P - 1 + j], full, P + j, P, min_new)
-                if j == 0:
-                    first = sc
-                lp = torch.log_softmax(sc, -1).gather(1, full[:, P + j:P + j + 1])[:, 0]
-                live = torch.as_tensor([j < len(g) for g in gens], device=dev)
-                tot += torch.where(live, lp.double(), torch.zeros_like(tot))
-            avg = [float(tot[i]) / len(g) if g else 0.0 for i, g in enumerate(gens)]
-            if P0 > 1:
-                nsp = torch.softmax(logits[:, P - P0], -1)[:, nts - 1]
-            else:
-                nsp = torch.softmax(first, -1)[:, nts - 1]
-            return avg, nsp.tolist()
-
-        def beam_no_speech(prefill, ids, P, min_new, nb):
-            """P(<|nospeech|>) of a beam-search pass as the reference's `_need_fallback` reads it.  prefill f32 / bf16 [r, P, V]: the
-            prompt-prefill logits of each utterance's beam 0.  With a decoder prompt of several start tokens
-            `WhisperNoSpeechDetection` runs the model on its own, unexpanded inputs: one row per utterance, the softmax at the
-            <|startoftranscript|> position.  With a single start token it keeps the processor scores of the first step, which in
-            beam search are the r * nb expanded rows (log-probabilities, so `exp`, not renormalised after the other processors), and
-            `_need_fallback` indexes that tensor with the UTTERANCE index (`no_speech_prob[index]`): utterance i is judged by
-            expanded row i, i.e. by utterance i // nb.  Reproduced here as it is."""
-            r = ids.shape[0]
-            if P0 > 1:
-                return torch.softmax(prefill[:, P - P0].float(), -1)[:, nts - 1].tolist()
-            lp = processed(torch.log_softmax(prefill[:, P - 1].float(), -1), ids, P, P, min_new)
-            per_row = lp[:, nts - 1].exp().tolist()
-            return [per_row[i // nb] for i in range(r)]
-
-        def ratio(tokens):
-            nbytes = int(math.log2(V) / 8) + 1
-            raw = b"".join(int(x).to_bytes(nbytes, "little") for x in tokens)
-            return len(raw) / len(zlib.compress(raw))
-
-        segments = [[] for _ in range(B)]
-        prompt = [int(x) for x in prompt_ids] if prompt_ids is not None else None
-        first_segment_prompt = bool(prompt) and not prompt_all_segments
-        if first_segment_prompt:
-            body = prompt[1:] if (prev_sot is not None and prompt[0] == prev_sot) else prompt
-            segments = [[{"tokens": list(body)}] for _ in range(B)]
-        do_cond = [bool(condition_on_prev_tokens)] * B
-        if not hasattr(self, "_seek_decoders"):
-            self._seek_decoders = {}           # reused by later calls (pseudo-labelling decodes batch after batch)
-        decoders = self._seek_decoders
-        # (utterance, first frame, average log-probability, no-speech probability) of every scored pass over a window, in order
-        window_scores = self.last_window_scores = []
-
-        def strip_pad(seq):
-            if seq and seq[-1] == pad:     # TF:1064-1071: drop the padding (all but one EOS when pad == EOS)
-                npad = sum(1 for x in seq if x == pad) - (1 if pad == eos else 0)
-                if npad:
-                    seq = seq[:-npad]
-            return seq
-
-        def judge(gen, avg, nsp):
-            """(decode again at the next temperature, skip the window) of one decoded window (TF:1243-1287)."""
-            fallback = skip = False
-            if compression_ratio_threshold is not None and gen and ratio(gen) > compression_ratio_threshold:
-                fallback = True
-            if logprob_threshold is not None and avg < logprob_threshold:
-                fallback = True
-            if no_speech_threshold is not None and avg < logprob_threshold and nsp > no_speech_threshold:
-                fallback, skip = False, True
-            return fallback, skip
-
-        if slots is not None:
-            # ---- the seek loop as a slot schedule: every (utterance, window) is a SlotDecoder job
-            from .decoding import SeekWindowSource, SlotDecoder
-            N = int(slots)
-            if callable(init_tokens) and len({len(r) for r in init}) > 1:      # (given rows were judged before the encoder ran)
-                raise NotImplementedError("the timestamp seek loop on slots needs decoder prompts of one length (init_tokens rows "
-                                          "of different lengths)")
-            P = len(prompt or []) + P0
-            per_pass = []                  # lengths(P) of an utterance's k-th window: the lockstep loop asks once per pass
-
-            def job(b, k):
-                while len(per_pass) <= k:
-                    per_pass.append(lengths(P))
-                if per_pass[k][1] != per_pass[0][1]:
-                    raise NotImplementedError("the timestamp seek loop on slots needs one min_new_tokens for every window")
-                return (prompt or []) + list(init[b]), per_pass[k][0], P - P0
-
-            def encode(take):
-                enc, _ = eng.encode(window(take), save=False)
-                return enc[:len(take) * d.max_src].view(len(take), d.max_src, -1)
-            job(0, 0)
-            min_new = per_pass[0][1]
-            key = ("slots", N, eos, pad, nts, max_initial_timestamp_index, tuple(suppress_tokens or ()),
-                   tuple(begin_suppress_tokens or ()), min_new, int(check_every), cross_kv_dtype, use_graphs, need_scores)
-            # Slot decoders are kept apart from the lockstep loop's (whose many batch sizes must not push them out).  Each owns its
-            # K/V caches -- N slots x (max_target_positions self rows + max_source_positions cross rows) x 2 d_model per decoder
-            # layer: 0.6 GB per layer at 64 slots of d_model 1280 in bf16, 20 GB for large-v3's 32 layers -- and its graphs, so
-            # only `seek_slot_decoders_max` (2: one configuration and a variant) stay alive; set the attribute to keep more.
-            slot_decoders = self.__dict__.setdefault("_seek_slot_decoders", {})
-            dec = slot_decoders.get(key)
-            if dec is None:
-                while len(slot_decoders) >= max(1, int(getattr(self, "seek_slot_decoders_max", 2))):
-                    slot_decoders.pop(next(iter(slot_decoders)))
-                dec = slot_decoders[key] = SlotDecoder(
-                    eng, N, d.max_tgt, eos, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-                    timestamp_rules=ts_rules, min_new_tokens=min_new, pad_token_id=pad, use_graphs=use_graphs,
-                    check_every=check_every, cross_kv_dtype=cross_kv_dtype, scores=need_scores,
-                    nsp_col=nts - 1 if need_scores else None)
-            source = SeekWindowSource([b for b in range(B) if seek[b] < max_frames[b]], N, encode, job)
-            steps0 = dec.steps
-            for res in dec.run(source):
-                b, seq = res[0], strip_pad(res[1][P:].tolist())
-                avg = nsp = None
-                if need_scores:
-                    avg, nsp = (float(res[2]) / len(seq) if seq else 0.0), float(res[3])
-                    window_scores.append((b, seek[b], avg, nsp))
-                _, skip = judge(seq, avg, nsp)         # (one temperature: nothing to fall back to)
-                snf = min(max_frames[b] - seek[b], W)
-                if skip:
-                    seek[b] += snf
-                else:
-                    segs, offset = G.retrieve_segment(seq[:-1] if (seq and seq[-1] == eos) else seq, tb, snf,
-                                                      time_offset=seek[b] * 0.01, with_idxs=False)
-                    seek[b] += offset
-                    segments[b] += segs
-                source.ended(b, seek[b] < max_frames[b])
-            self.last_seek_stats = dict(source.stats, steps=dec.steps - steps0)
-            return [sg[1:] for sg in segments] if first_segment_prompt else segments
-
-        while any(seek[b] < max_frames[b] for b in range(B)):
-            rows = [b for b in range(B) if seek[b] < max_frames[b]]
-            snf = {b: min(max_frames[b] - seek[b], W) for b in rows}
-            enc_all, _ = eng.encode(window(rows), save=False)
-            enc_all = enc_all[:len(rows) * d.max_src].view(len(rows), d.max_src, -1)
-            # decoder prompts (TF:1853-1918)
-            prompts = {}
-            cond_now = any(do_cond[b] for b in rows) and len(segments[0]) > 0
-            for b in rows:
-                pre = []
-                if cond_now:
-                    if prev_sot is None:
-                        raise ValueError("condition_on_prev_tokens needs prev_sot_token_id in the generation config")
-                    if do_cond[b] and segments[b]:
-                        for sg in segments[b]:
-                            tk = sg["tokens"]
-                            pre += tk[:-1] if (len(tk) > 2 and tk[-2] >= tb) else tk
-                        pre = pre[-cut_off:]
-                    pre = (list(prompt) if (prompt and prompt_all_segments) else [prev_sot]) + pre
-                elif prompt:
-                    pre = list(prompt)
-                prompts[b] = pre + list(init[b])
-            accepted, window_ts = {}, {}
-            # (the reference left-pads the batch to its longest prompt and derives the lengths from that, TF:835-840)
-            max_new, min_new = lengths(max(len(prompts[b]) for b in rows))
-            for P in sorted({len(prompts[b]) for b in rows}):
-                group = [b for b in rows if len(prompts[b]) == P]
-                pending = list(group)
-                for ti, temp in enumerate(temps):
-                    pos = [rows.index(b) for b in pending]
-                    enc = enc_all[pos].reshape(len(pending) * d.max_src, -1).contiguous()
-                    ids = torch.as_tensor([prompts[b] for b in pending], dtype=torch.long, device=dev)
-                    if temp > 0.0:
-                        out = sample(enc, ids, max_new, min_new, temp)[:, P:].tolist()
-                    elif assistant is not None:
-                        from .decoding import assisted_greedy_decode
-                        a_eng, a_encode = assistant
-                        enc_a = enc.to(a_eng.lowp) if a_encode is None else a_encode(window(pending))
-                        out, nd, na = assisted_greedy_decode(
-                            eng, a_eng, enc, enc_a, ids, max_new, int(num_assistant_tokens), eos,
-                            suppress_tokens=suppress_tokens, min_new_tokens=min_new, pad_token_id=pad,
-                            timestamp_rules=dict(begin_index=P, no_timestamps_token_id=nts,
-                                                 max_initial_timestamp_index=max_initial_timestamp_index))
-                        self.last_drafted = getattr(self, "last_drafted", 0) + nd
-                        self.last_accepted = getattr(self, "last_accepted", 0) + na
-                        out = torch.cat([out, torch.full((out.shape[0], P + max_new - out.shape[1]), pad,
-                                                         dtype=out.dtype, device=dev)], 1)[:, P:].tolist()
-                    elif int(num_beams) > 1:
-                        from .decoding import beam_search_decode
-                        out = beam_search_decode(
-                            eng, enc, ids, max_new, int(num_beams), eos, pad_token_id=pad, suppress_tokens=suppress_tokens,
-                            begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new,
-                            length_penalty=float(length_penalty), early_stopping=early_stopping,
-                            timestamp_rules=dict(begin_index=P, no_timestamps_token_id=nts,
-                                                 max_initial_timestamp_index=max_initial_timestamp_index),
-                            return_scores=need_scores)
-                        if need_scores:
-                            out, beam_sc, prefill = out
-                            beam_scored = (beam_sc.tolist(), beam_no_speech(prefill, ids, P, min_new, int(num_beams)))
-                        out = out[:, P:].tolist()
-                    else:
-                        key = (len(pending), P, max_new, eos, pad, nts, max_initial_timestamp_index,
-                               tuple(suppress_tokens or ()), tuple(begin_suppress_tokens or ()), rep_pen, ngram, sequence_bias)
-                        dec = decoders.get(key)
-                        if dec is None:
-                            if len(decoders) >= 4:     # (a decoder owns its K/V caches: keep a handful alive)
-                                decoders.pop(next(iter(decoders)))
-                            dec = decoders[key] = GreedyDecoder(
-                                eng, len(pending), P + max_new, eos_token_id=eos, suppress_tokens=suppress_tokens,
-                                begin_suppress_tokens=begin_suppress_tokens, use_graphs=False, pad_token_id=pad,
-                                check_every=4,      # eager passes: stop within 3 steps of the last row's EOS
-                                timestamp_rules=dict(begin_index=P, no_timestamps_token_id=nts,
-                                                     max_initial_timestamp_index=max_initial_timestamp_index),
-                                soft=hist_soft)
-                        full = dec.run(enc, ids, max_new, min_new)
-                        if token_timestamps is not None:
-                            from .alignment import extract_token_timestamps
-                            nf = token_timestamps["num_frames"]
-                            ts = extract_token_timestamps(
-                                self, self._trim_finished(full, P, eos, pad), enc, token_timestamps["alignment_heads"],
-                                None if nf is None else [nf[b] - seek[b] for b in pending], P,
-                                token_timestamps["time_precision"]).cpu()
-                            for i, b in enumerate(pending):
-                                window_ts[b] = ts[i]
-                        out = full[:, P:].tolist()
-                    gens = [strip_pad(seq) for seq in out]
-                    avg = nsp = None
-                    if need_scores and temp == 0.0 and int(num_beams) > 1 and assistant is None:
-                        avg, nsp = beam_scored           # the hypotheses' own scores: no teacher-forced pass (TF:1261-1264)
-                    elif need_scores:
-                        avg, nsp = scores_of(enc, ids, gens, min_new)
-                    if need_scores:
-                        window_scores.extend((b, seek[b], float(avg[i]), float(nsp[i])) for i, b in enumerate(pending))
-                    again = []
-                    for i, b in enumerate(pending):
-                        fallback, skip = judge(gens[i], avg[i] if need_scores else None, nsp[i] if need_scores else None)
-                        seq = gens[i][:-1] if (gens[i] and gens[i][-1] == eos) else gens[i]
-                        accepted[b] = (seq, skip)
-                        do_cond[b] = bool(condition_on_prev_tokens) and temp < 0.5
-                        if fallback:
-                            again.append(b)
-                    if not again or ti == len(temps) - 1:
-                        break
-                    pending = again
-            for b in rows:
-                seq, skip = accepted[b]
-                if skip:
-                    seek[b] += snf[b]
-                    continue
-                segs, offset = G.retrieve_segment(seq, tb, snf[b], time_offset=seek[b] * 0.01,
-                                                  with_idxs=token_timestamps is not None)
-                if token_timestamps is not None:
-                    P = len(prompts[b])
-                    # TF:800-802: the window's offset in seconds, a double; added to the float32 row as the reference adds it
-                    t_off = torch.tensor(seek[b], dtype=torch.float64) * token_timestamps["time_precision"] / 2
-                    for sg in segs:
-                        i0, i1 = sg["idxs"]
-                        sg["idxs"] = (P + i0, P + i1)
-                        sg["result"] = {"token_timestamps": window_ts[b]}
-                        sg["token_timestamps"] = window_ts[b][P + i0:P + i1] + t_off
-                seek[b] += offset
-                segments[b] += segs
-        return [sg[1:] for sg in segments] if first_segment_prompt else segments
-
-    def _generate_seek_loop(self, input_features, attention_mask, gc, language, task, is_multilingual, prompt_ids, kwargs,
-                            use_graphs, return_dict_in_generate, num_beams, fallback_args=None, return_segments=False,
-                            token_ts=None, history=None, seek_slots=None):
-        """Timestamp-driven multi-pass transcription: `WhisperGenerationMixin.generate` steps 5-7 (TF:745-968) with
-        temperature 0 and no fallback thresholds -- every utterance keeps a `seek` position in mel frames; each pass
-        decodes the next <= 30 s window of every unfinished utterance with the timestamp rules, `retrieve_segment`
-        splits the tokens at consecutive timestamp pairs and advances `seek` to the last predicted end of segment (or
-        past the window).  Inputs of any length ([B, n_mels, frames]; batches of long inputs need `attention_mask`).
-        Returns the concatenated segment tokens per utterance, right-padded with pad_token_id (the reference's plain
-        return value), a GenerateOutput with `.sequences` and `.segments` (return_dict_in_generate), or -- with
-        `return_segments=True`, like the reference (TF:generate, "8. If we return all segments") -- a plain dict
-        {"sequences", "segments"}: per utterance the list of {"start", "end", "tokens"} in seconds / token ids (the
-        reference's entries also carry the raw GenerationMixin output of their window under "result" and "idxs")."""
-        from . import generation as G
-        eng, d = self.engine, self.dims
-        B, _, frames = input_features.shape
-        dev = input_features.device
-        W = 2 * d.max_src
-        if kwargs.get("decoder_input_ids") is not None:
-            raise NotImplementedError("decoder_input_ids with the timestamp seek loop are not implemented on the MI355X "
-                                      "path (pass prompt_ids, or force_unique_generate_call=True for a single window)")
-        all_segments = getattr(gc, "prompt_condition_type", "first-segment") == "all-segments"
-        if all_segments and not (fallback_args or {}).get("condition_on_prev_tokens"):
-            raise ValueError("Make sure to set `condition_on_prev_tokens=True` when setting "
-                             "`prompt_condition_type='all-segments'`.")
-        if kwargs.get("use_cache", True) is False:
-            raise NotImplementedError("the timestamp seek loop runs on the KV-cache decoder only")
-        assistant, begin_suppress_loop = None, (list(gc.begin_suppress_tokens) if gc.begin_suppress_tokens else None)
-        am = kwargs.get("assistant_model")
-        if am is not None:
-            if num_beams != 1:
-                raise ValueError("assistant_model cannot be combined with beam search (TF raises the same)")
-            am._sync_shadow()
-            shared = _assistant_shares_encoder(am, d)     # (a distilled student keeps the teacher's encoder)
-            a_encode = None if shared else \
-                (lambda f: am.engine.encode(f.to(torch.float32).contiguous(), save=False)[0])
-            assistant = (am.engine, a_encode)
-            begin_suppress_loop = None     # TF:719-721: with an assistant the model must be able to return EOS right away
-            self.last_drafted = self.last_accepted = 0
-        if not hasattr(gc, "no_timestamps_token_id"):
-            raise ValueError("You are trying to return timestamps, but the generation config is not properly set. Make "
-                             "sure to initialize the generation config with the correct attributes that are needed "
-                             "such as `no_timestamps_token_id`.")
-        gc.return_timestamps = True
-        G.set_language_and_task(gc, language, task, is_multilingual)
-        if B > 1 and frames > W and attention_mask is None:
-            raise ValueError("When doing batched long-form audio transcription, make sure to pass an `attention_mask`. "
-                             "You can retrieve the `attention_mask` by doing `processor(audio, ..., "
-                             "return_attention_mask=True)` ")
-        if B > 1 and frames > W:
-            max_frames = [int(x) for x in attention_mask.sum(-1).tolist()]
-        else:
-            max_frames = [frames] * B
-        def detect_on(enc0):
-            return self._detect_language(enc0, B, gc)
-        eos, pad = gc.eos_token_id, gc.pad_token_id
-        if isinstance(eos, (list, tuple)):
-            eos = eos[0]
-        if eos is None:
-            raise ValueError("return_timestamps=True needs eos_token_id in the generation config")
-        if pad is None:
-            pad = eos
-        explicit_max_length = "max_length" in kwargs
-
-        def lengths(P):
-            max_new, min_new = G.resolve_lengths(gc, P, d.max_tgt, explicit_max_length)
-            if gc.max_new_tokens is None:          # TF:1932-1940 mutates max_length on every pass
-                gc.max_length = min(gc.max_length + min(d.max_tgt // 2 - 1, P), d.max_tgt)
-            return max_new, min_new
-        segments = self.seek_decode(input_features, max_frames, lambda det: G.retrieve_init_tokens(gc, B, det), lengths,
-                                    eos, pad, int(gc.no_timestamps_token_id),
-                                    getattr(gc, "max_initial_timestamp_index", None),
-                                    list(gc.suppress_tokens) if gc.suppress_tokens else None,
-                                    begin_suppress_loop,
-                                    detect_language=detect_on, prev_sot_token_id=getattr(gc, "prev_sot_token_id", None),
-                                    prompt_ids=(prompt_ids.tolist() if torch.is_tensor(prompt_ids) else prompt_ids),
-                                    prompt_all_segments=all_segments and prompt_ids is not None,
-                                    num_beams=num_beams, assistant=assistant,
-                                    num_assistant_tokens=(getattr(gc, "num_assistant_tokens", None) or getattr(
-                                        getattr(am, "generation_config", None), "num_assistant_tokens", None) or 5),
-                                    length_penalty=1.0 if getattr(gc, "length_penalty", None) is None else gc.length_penalty,
-                                    early_stopping=getattr(gc, "early_stopping", False) or False,
-                                    token_timestamps=token_ts, **(history or {}), **(fallback_args or {}), **(seek_slots or {}))
-        rows_out = [[tok for sg in segments[b] for tok in sg["tokens"]] for b in range(B)]
-        width = max((len(r) for r in rows_out), default=0)
-        seqs = torch.full((B, width), pad, dtype=torch.long, device=dev)
-        for b, r in enumerate(rows_out):
-            if r:
-                seqs[b, :len(r)] = torch.as_tensor(r, dtype=torch.long, device=dev)
-        if token_ts is not None:
-            # `_pad_to_max_length` (TF:150-235): per utterance the windows' own values of its segments' tokens (without the time
-            # offsets, as the reference concatenates them), right-padded with the row's last value
-            rows_ts = [[sg["result"]["token_timestamps"][sg["idxs"][0]:sg["idxs"][1]] for sg in segments[b]] for b in range(B)]
-            ts = torch.zeros((B, width), dtype=torch.float32)
-            for b, parts in enumerate(rows_ts):
-                if parts:
-                    row = torch.cat(parts, -1)
-                    ts[b, :len(row)] = row
-                    if len(row):
-                        ts[b, len(row):] = row[-1]
-            out = {"sequences": seqs, "token_timestamps": ts.to(dev)}
-            rdig = return_dict_in_generate or getattr(gc, "return_dict_in_generate", False)
-            if return_segments or rdig:          # TF:945-949: return_dict_in_generate switches return_segments on
-                out["segments"] = segments
-            return G.GenerateOutput(seqs, token_timestamps=out["token_timestamps"], segments=segments) if rdig else out
-        if return_segments:
-            return {"sequences": seqs, "segments": segments}
-        if return_dict_in_generate or getattr(gc, "return_dict_in_generate", False):
-            out = G.GenerateOutput(seqs)
-            out.segments = segments
-            return out
-        return seqs
+        from . import seek
+        return seek.seek_decode(self, dict(
+            input_features=input_features, max_frames=max_frames, init_tokens=init_tokens, lengths=lengths, eos=eos, pad=pad,
+            no_timestamps_token_id=no_timestamps_token_id, max_initial_timestamp_index=max_initial_timestamp_index,
+            suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens, detect_language=detect_language,
+            temperatures=temperatures, compression_ratio_threshold=compression_ratio_threshold,
+            logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold,
+            condition_on_prev_tokens=condition_on_prev_tokens, prev_sot_token_id=prev_sot_token_id, prompt_ids=prompt_ids,
+            prompt_all_segments=prompt_all_segments, num_beams=num_beams, length_penalty=length_penalty,
+            early_stopping=early_stopping, assistant=assistant, num_assistant_tokens=num_assistant_tokens,
+            token_timestamps=token_timestamps, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+            sequence_bias=sequence_bias, slots=slots, check_every=check_every, cross_kv_dtype=cross_kv_dtype,
+            use_graphs=use_graphs))
 
     # -- helpers of generate ----------------------------------------------------------------------------------------
-    @staticmethod
-    def _trim_finished(seqs, P, eos, pad):
-        """GenerationMixin stops as soon as every row has emitted EOS: drop the all-padding columns a decoder that
-        checks the stop condition every few steps (HIP-graph replay) may have appended."""
-        if eos is None or seqs.shape[1] <= P:
-            return seqs
-        gen = seqs[:, P:]
-        is_eos = gen == eos
-        n = gen.shape[1]
-        first = torch.where(is_eos.any(1), is_eos.float().argmax(1) + 1, torch.full((gen.shape[0],), n, device=gen.device))
-        keep = int(first.max().item())
-        return seqs[:, : P + keep]
-
     def _detect_language(self, enc, B, gc):
         """TF:1610-1674 `detect_language`: one decoder step on <|startoftranscript|>, argmax over the language ids."""
         d = self.dims
@@ -1847,29 +1156,6 @@ class WhisperForConditionalGeneration(nn.Module):
         mask = torch.full((d.vocab,), float("-inf"), device=enc.device)
         mask[lang_ids] = 0.0
         return (sc + mask).argmax(-1).tolist()
-
-    def _greedy_no_cache(self, enc, ids, max_new, min_new, eos, pad, suppress, begin_suppress):
-        """Greedy search that re-decodes the whole prefix at every step (no KV cache): the cross-check of the cached
-        decoder."""
-        from .decoding import processed_scores, token_mask
-        eng, d = self.engine, self.dims
-        B, dev = ids.shape[0], ids.device
-        done = torch.zeros(B, dtype=torch.bool, device=dev)
-
-        sup, bsup = (token_mask(t, d.vocab, dev) for t in (suppress, begin_suppress))
-        for step in range(max_new):
-            T = ids.shape[1]
-            logits, _ = eng.decode(ids.contiguous(), enc, save=False)
-            sc = logits[: B * T, : d.vocab].view(B, T, -1)[:, -1].float()
-            nxt = processed_scores(sc, ids, T, begin_index=T - step, eos=eos, no_eos=step < min_new, first=step == 0, suppress=sup,
-                                   begin_suppress=bsup).argmax(-1)
-            if eos is not None:
-                nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
-                done |= nxt == eos
-            ids = torch.cat([ids, nxt[:, None]], 1)
-            if eos is not None and bool(done.all()):
-                break
-        return ids
 
 
 @dataclass
