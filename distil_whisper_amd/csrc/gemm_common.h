@@ -334,10 +334,13 @@ __device__ __forceinline__ void gemm_lds_barrier() {
 // (lane & 15 = row of the 16-row block, register r = column 4 (lane >> 4) + r of the 16-column block).  Either way a lane holds
 // FN * 4 "quads" (4 consecutive columns of one row) per 32-row slab; quad q of slab i sits at row qrow(q) + lane part, column
 // qcol(q) + lane part of the slab.
-template <int FM, int FN, int TN, int PFDIST = 0, class Hook = GemmNoHook, bool SWZ = false, int LAY = 32, int JOFF = 0, class Acc = f32x16[FM][FN]>
+// TAILED (the grouped weight-gradient kernel, gemm_wgrad_group.hip): the wave's last 32-row slab does not follow the others -- it
+// sits `tail_rows` output rows further down (wave-uniform).  Interior tiles only: the general walk does not know the displacement.
+template <int FM, int FN, int TN, int PFDIST = 0, class Hook = GemmNoHook, bool SWZ = false, int LAY = 32, int JOFF = 0, class Acc = f32x16[FM][FN],
+          bool TAILED = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* smem, int wave, int lane,
                                               int m0_, int wm0_, int n0_, int wn0_, int ks_, Hook hook = Hook(),
-                                              const float* lds_bias = nullptr) {
+                                              const float* lds_bias = nullptr, int tail_rows = 0) {
     // lds_bias: the tile's bias slice (BN floats from column n0) staged in LDS by the caller at the start of the tile
     // (interior tiles only).  A bias read from global memory here is an ordinary load whose vmcnt wait also drains every
     // operand DMA the caller has in flight for the NEXT tile (the counter retires in order).
@@ -466,7 +469,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
             auto side_load = [&](auto gc) __attribute__((always_inline)) {   // gc: linear row-group index = slab * NIT + group
                 constexpr int gi = decltype(gc)::value;
                 constexpr int slot = gi % PFD;
-                constexpr long rg = (gi / NIT) * 32 + (gi % NIT) * RPI;              // first row of the row group in the wave tile
+                constexpr long rg0 = (gi / NIT) * 32 + (gi % NIT) * RPI;             // first row of the row group in the wave tile
+                long rg = rg0;
+                if constexpr (TAILED && gi / NIT == FM - 1) rg += tail_rows;
                 // gelu'(z) -- 491 MB per dX-of-fc2 launch, read once -- is loaded with the non-temporal hint: 338.7 -> 337.2 ms per
                 // step against a build with plain loads in one process (round 6); the hint on the residual as well was within noise
                 if (want_z) zq[slot] = __builtin_nontemporal_load((const bf16x4*)(zg_u + rg * p.ldzg * 2 + l_zg));
@@ -502,7 +507,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     const int rl = it * RPI + pr;
-                    constexpr long rg = i * 32 + it * RPI;
+                    constexpr long rg0 = i * 32 + it * RPI;
+                    long rg = rg0;
+                    if constexpr (TAILED && i == FM - 1) rg += tail_rows;
                     f32x4 a4;
                     if constexpr (RF) a4 = a4s[it % RG];
                     else a4 = *(const f32x4*)(patch + rl * PLD + (SWZ ? (((pc >> 2) ^ (rl & 15)) << 2) : pc));
@@ -646,7 +653,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, Acc& acc, char* sm
             // (the 320-row tile -- FM = 5, 160 accumulator registers -- and the 16-wave kernels keep the run-time walk for
             // the flavours with side inputs: with one walk per flavour the 320-row kernel's register allocation falls
             // apart, 763 spills against 12)
-            if constexpr (FM == 5) {
+            if constexpr (FM == 5 && !TAILED) {      // (TAILED: fp32 stores with or without the fp32 read-add, the run-time walk)
                 switch (gemm_epi_flavour(p)) {
                     DW_EPI_CASE16(0);
                     DW_EPI_CASE16(EPI_BIAS);

@@ -308,6 +308,9 @@ class WhisperEngine:
         self.ldv = _rup(self.dims.vocab, 64)
         self.wgrad_stream = None   # torch.cuda.Stream: weight-gradient GEMMs / bias column sums of the backward go there
         self._wgrad_held, self._wgrad_fences = [], []
+        self._wgrad_pending = []       # (dy, x, gout) of the layer in its backward (group_wgrad)
+        self._wgrad_collect = True     # False: the layer in its backward has shown a matrix that does not fit a group
+        self.wgrad_groups_issued = 0   # layers whose weight gradients went out as one grouped launch (tests, tools)
         # Forward-only decoder passes (the frozen teacher) may run their GEMMs over a row count padded to a multiple of
         # 320 when that costs <= 1/32 extra rows: M = 32 x 447 = 14304 -> 14400 = 45 row tiles of the 320 x 256 GEMM
         # kernel, ONE round of 225 workgroups for N = 1280 where the 128-tile kernel needs 4.4 rounds of 1120.  Pad rows
@@ -499,6 +502,18 @@ class WhisperEngine:
 
     def _wgrad(self, dy, x, gout, gbias, R, bias_cols=None):
         """gout (+)= dy^T . x over the (padded) token dimension; gbias (+)= column sums of dy."""
+        if self.group_wgrad and self._wgrad_collect and gout is not None and hasattr(self.ops, "wgrad_group"):
+            # the layer's weight-gradient GEMMs are collected and issued in one launch at the layer boundary (_wgrad_flush); the
+            # bias column sums stay where they are.  A matrix that does not fit the group ends the collection: what was collected
+            # goes out as it would have without group_wgrad, and so does the rest of the layer -- never a part of a layer each way.
+            if self.ops.wgrad_group_ok(self._wgrad_pending + [(dy, x, gout)]):
+                self._wgrad_pending.append((dy, x, gout))
+                if gbias is None:
+                    return
+                gout = None
+            else:
+                self._wgrad_collect = False
+                self._wgrad_flush(layer_done=False)
         ws = self.wgrad_stream
         if ws is not None:
             # Weight gradients are off the critical path of the backward (nothing below reads them): issued on a second
@@ -525,10 +540,40 @@ class WhisperEngine:
     wgrad_overwrite = False   # set by the trainer around a backward that follows zero_small_grads(): every weight matrix handed to
                               # _wgrad gets exactly one contribution per backward, so the split-K combine may store instead of add
     wgrad_lag = 2     # layers of weight-gradient work the side stream may be behind before the main stream waits for it
+    group_wgrad = True   # a layer's weight-gradient GEMMs in ONE launch of 320 x 256 tiles without K slices (ops.wgrad_group) where the
+                         # layer is eligible: up to four matrices over the same token rows, dimensions multiples of 320 / 256, at most
+                         # 256 tiles together -- the encoder layers at D = 1280.  Any other layer takes the launches of _wgrad_issue, whole.
+
+    def _wgrad_flush(self, layer_done=True):
+        """Issue the weight-gradient GEMMs _wgrad collected since the last layer boundary: one grouped launch, or -- the whole
+        layer -- one launch per matrix as without group_wgrad.  On the side stream when there is one (lifetime: _wgrad)."""
+        pending, self._wgrad_pending = self._wgrad_pending, []
+        grouped = self._wgrad_collect      # (_wgrad checked the group as it grew)
+        if layer_done:
+            self._wgrad_collect = True
+        if not pending:
+            return
+        self.wgrad_groups_issued += int(grouped)
+
+        def issue():
+            if grouped:
+                self.ops.wgrad_group(pending, overwrite=self.wgrad_overwrite)
+            else:
+                for dy, x, gout in pending:
+                    self._wgrad_issue(dy, x, gout, None, 0, None)
+        ws = self.wgrad_stream
+        if ws is not None:
+            ws.wait_stream(torch.cuda.current_stream(pending[0][0].device))
+            with torch.cuda.stream(ws):
+                issue()
+            self._wgrad_held += [t for dy, x, _ in pending for t in (dy, x)]
+        else:
+            issue()
 
     def _wgrad_fence(self):
-        """Layer boundary of the backward: mark the side stream's position; tensors handed to it `wgrad_lag` boundaries
-        ago are released after the main stream has waited for that mark."""
+        """Layer boundary of the backward: issue the layer's collected weight-gradient GEMMs, then mark the side stream's position;
+        tensors handed to it `wgrad_lag` boundaries ago are released after the main stream has waited for that mark."""
+        self._wgrad_flush()
         ws = self.wgrad_stream
         if ws is None or not (self._wgrad_held or self._wgrad_fences):
             return
@@ -555,6 +600,7 @@ class WhisperEngine:
     def join_wgrad_stream(self):
         """The main stream waits for every weight-gradient kernel issued so far (before the optimizer, the gradient
         all-reduce of a finished range, or any other reader of the gradient buffer)."""
+        self._wgrad_flush()
         if self.wgrad_stream is not None:
             torch.cuda.current_stream(self.st.P.device).wait_stream(self.wgrad_stream)
         self._wgrad_fences.clear()
@@ -1164,6 +1210,8 @@ class WhisperEngine:
                                                 # over the layer's rectangular buffers between a scatter and a gather
         tr = st.is_trainable(f"{p}.fc1.weight")
         cross = "x1" in lc
+        if cross:       # (seven matrices, two token counts: no group -- the launches of _wgrad_issue where they always were)
+            self._wgrad_collect = False
         pd, pa = lc.get("pd", 0.0), lc.get("pa", 0.0)
 
         def enter(dy_, kind):

@@ -37,6 +37,15 @@ class DwGemm(C.Structure):
     ]
 
 
+class DwWgradProblem(C.Structure):
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("c", C.c_void_p), ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64),
+                ("m", C.c_int32), ("n", C.c_int32)]
+
+
+WGRAD_GROUP_MAX = 4       # DW_WGRAD_GROUP_MAX
+WGRAD_GROUP_CUS = 256     # tiles of a group: one round of the CUs (include/dwamd.h dw_wgrad_group)
+
+
 class DwDecoderLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_g", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_g", "ln2_b", "wq", "bq", "wo2", "bo2", "ln3_g", "ln3_b",
@@ -80,6 +89,7 @@ _SIGS = {
                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "dw_layernorm_bwd_ws_bytes": ([C.c_int, C.c_int], C.c_int),
     "dw_reduce_slices_ld": ([C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
+    "dw_wgrad_group": ([C.POINTER(DwWgradProblem), C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "dw_layernorm_fwd_ld": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                              C.c_int, C.c_float, C.c_int64, C.c_int64, C.c_void_p], C.c_int),
     "dw_layernorm_bwd_ld": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -408,6 +418,43 @@ class HipOps:
                     f"{' sk%d' % g.split_k if g.split_k else ''}")
         self._t1(e0, key, 2.0 * M * N * K)
         return (out, z) if want_z else out
+
+    @staticmethod
+    def wgrad_group_ok(triples):
+        """What dw_wgrad_group accepts (include/dwamd.h), restated for the caller that decides between one grouped launch and
+        today's launches: `triples` = [(dy [k, m], x [k, n], out [m, n] fp32)], all over the same k."""
+        if not 1 <= len(triples) <= WGRAD_GROUP_MAX:
+            return False
+        k, tiles = triples[0][0].shape[0], 0
+        for dy, x, out in triples:
+            m, n = dy.shape[1], x.shape[1]
+            if dy.shape[0] != k or x.shape[0] != k or tuple(out.shape) != (m, n) or m % 320 or n % 256 or k % 64:
+                return False
+            if dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or out.dtype != torch.float32:
+                return False
+            if dy.stride(1) != 1 or x.stride(1) != 1 or out.stride(1) != 1 or dy.stride(0) % 8 or x.stride(0) % 8 or out.stride(0) % 4:
+                return False
+            if dy.data_ptr() % 16 or x.data_ptr() % 16 or out.data_ptr() % 16:
+                return False
+            if k * dy.stride(0) * 2 >= 0x7fffffff or k * x.stride(0) * 2 >= 0x7fffffff:
+                return False
+            tiles += (m // 320) * (n // 256)
+        return tiles <= WGRAD_GROUP_CUS
+
+    def wgrad_group(self, triples, overwrite=False):
+        """out_i (+)= dy_i^T . x_i for the (dy, x, out) of `triples` in ONE launch of 320 x 256 tiles without K slices
+        (dw_wgrad_group).  overwrite: the outputs are stored, not added to."""
+        arr = (DwWgradProblem * len(triples))()
+        flops = 0.0
+        for q, (dy, x, out) in zip(arr, triples):
+            q.a, q.b, q.c = dy.data_ptr(), x.data_ptr(), out.data_ptr()
+            q.lda, q.ldb, q.ldc = dy.stride(0), x.stride(0), out.stride(0)
+            q.m, q.n = dy.shape[1], x.shape[1]
+            flops += 2.0 * q.m * q.n * dy.shape[0]
+        e0 = self._t0()
+        self._chk(self.lib.dw_wgrad_group(arr, len(triples), triples[0][0].shape[0], 0 if overwrite else 1, self._stream()),
+                  f"wgrad_group of {len(triples)}")
+        self._t1(e0, "gemm_g320_TT", flops)
 
     def decode_pass(self, desc):
         """One decoder pass of cached greedy decoding through the single C entry point dw_decode_step (every launch of

@@ -107,6 +107,25 @@ int dw_reduce_slices(const float* part, int64_t stride, int slices, float* out, 
 /* The same over [rows][cols] matrices whose rows are ld_part (slabs, slice_stride elements apart) / ld_out elements apart. */
 int dw_reduce_slices_ld(const float* part, int64_t slice_stride, int64_t ld_part, int slices, float* out, int64_t ld_out,
                         int rows, int cols, int accumulate, void* stream);
+/* Grouped weight gradients: C_i (+)= A_i^T . B_i for 1 <= count <= DW_WGRAD_GROUP_MAX problems in ONE launch, one 320 x 256 output
+ * tile per workgroup, no K slices and nothing to combine -- the weight matrices of a layer together fill one round of the CUs where
+ * each alone needs a split of k (csrc/gemm_wgrad_group.hip).  All problems share the contraction length k (the token rows); both
+ * operands are k-major bf16 as for dw_gemm_bf16 with trans_a && trans_b: a [k][lda] holds the m_i columns, b [k][ldb] the n_i.
+ * accumulate = 0: c_i is stored (whatever it held); 1: c_i += the product (every element read and written once by the same lane).
+ * Every output element is one fp32 chain over k in ascending order: deterministic, the same bits from every launch.
+ * DW_EINVAL, before any launch and with nothing written, unless: every m_i %% 320 == 0 and n_i %% 256 == 0 (both > 0); k > 0 and
+ * k %% 64 == 0; the tiles of the group sum(m_i / 320 * n_i / 256) number at most the CUs the persistent GEMMs occupy (256, or
+ * dw_debug_set key 9); k * lda_i * 2 and k * ldb_i * 2 are below 2^31 - 1 (31-bit buffer offsets); a_i, b_i and c_i are 16-byte
+ * aligned, lda_i and ldb_i multiples of 8 with lda_i >= m_i and ldb_i >= n_i, ldc_i a multiple of 4 with ldc_i >= n_i. */
+#define DW_WGRAD_GROUP_MAX 4
+typedef struct DwWgradProblem {
+    const void* a;   /* bf16 [k][lda] */
+    const void* b;   /* bf16 [k][ldb] */
+    float* c;        /* f32 [m][ldc] */
+    int64_t lda, ldb, ldc;
+    int32_t m, n;
+} DwWgradProblem;
+int dw_wgrad_group(const DwWgradProblem* problems, int count, int k, int accumulate, void* stream);
 
 /* ---- LayerNorm (TF:modeling_whisper.py:371,377,434,443,446,573,682), eps 1e-5, statistics in f32 ---------------
  * x [rows][cols] f32 or bf16 (x_dtype), y bf16 [rows][cols]; mean/rstd f32 [rows] (may be NULL for inference). */

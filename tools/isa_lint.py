@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "distil_whisper_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-munsafe-fp-atomics", "-S", "--cuda-device-only",
          "-I", os.path.join(ROOT, "include")]
-DEFAULT = ["gemm_wp8_m320", "gemm_wp8_nn", "gemm_wp8_nt", "gemm_wp16_nn", "gemm_wp16_tt", "attention", "norm"]
+DEFAULT = ["gemm_wp8_m320", "gemm_wp8_nn", "gemm_wp8_nt", "gemm_wp16_nn", "gemm_wp16_tt", "gemm_wgrad_group", "attention", "norm"]
 
 
 def kernels(asm):

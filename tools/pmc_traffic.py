@@ -31,6 +31,7 @@ CLASS_OF = [  # kernel symbol -> the per-class key bench.py / ops_hip.py use
     # kernels and not these patterns, so a third of the NN class and the whole weight-gradient class had no counter bytes
     (r"gemm_wp16_kernel<false, false", "gemm_t256_NN"), (r"gemm_wp16_kernel<false, true", "gemm_t256_NT"),
     (r"gemm_wp16_kernel<true, true", "gemm_t256_TT"), (r"gemm_wp16_kernel<true, false", "gemm_t256_TN"),
+    (r"wgrad_group_kernel", "gemm_g320_TT"),     # the grouped weight-gradient launch of a layer (gemm_wgrad_group.hip; ops_hip.wgrad_group)
     (r"gemm_skinny", "gemm_skinny"), (r"attn_fwd_kernel", "attn_fwd"), (r"attn_bwd_dkv", "attn_bwd_dkv"),
     (r"attn_bwd_dq", "attn_bwd_dq"), (r"attn_decode", "attn_decode"),
     (r"ln_fwd", "ln_fwd"), (r"ln_bwd", "ln_bwd"), (r"adamw", "adamw"), (r"loss_row", "loss"),
