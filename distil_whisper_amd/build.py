@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdwamd.so")
 SOURCES = ["gemm.hip", "gemm_tile256.hip", "gemm_tile128.hip", "gemm_wp8_nn.hip", "gemm_wp8_nt.hip", "gemm_wp8_m320.hip", "gemm_wp8_m128.hip",
-           "gemm_wp16_nn.hip", "gemm_wp16_tt.hip", "gemm_wp16_small.hip", "gemm_wgrad_group.hip", "gemm_skinny.hip", "attention.hip", "norm.hip", "loss.hip", "logmel.hip", "elementwise.hip", "optim.hip", "decode.hip", "beam.hip", "align.hip", "score.hip", "dropout.hip", "spec_augment.hip", "assist.hip", "slots.hip", "cross_kv8.hip"]
+           "gemm_wp16_nn.hip", "gemm_wp16_tt.hip", "gemm_wp16_small.hip", "gemm_wgrad_group.hip", "gemm_skinny.hip", "attention.hip", "norm.hip", "loss.hip", "logmel.hip", "elementwise.hip", "optim.hip", "decode.hip", "beam.hip", "align.hip", "score.hip", "dropout.hip", "spec_augment.hip", "assist.hip", "slots.hip", "cross_kv8.hip", "topk_distill.hip"]
 # -munsafe-fp-atomics: float atomicAdd becomes the hardware global_atomic_add_f32 instead of a CAS loop
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-munsafe-fp-atomics"]
 

@@ -20,7 +20,9 @@ import time
 
 import torch
 
+from . import topk_distill
 from .engine import LiveRows, ParamStore, WhisperDims, WhisperEngine
+from .topk_distill import TeacherTopK
 
 
 def shift_tokens_right(labels, pad_token_id, decoder_start_token_id):
@@ -241,17 +243,24 @@ class DistillationTrainer:
                  always_reduce=False, comm_watchdog_s=0.0, dropout=None, activation_dropout=None, dropout_seed=0,
                  spec_augment=None, augment_teacher=True):
         self.ops = ops
-        self.sdims, self.tdims = WhisperDims.from_any(student_dims), WhisperDims.from_any(teacher_dims)
+        # teacher_sd / teacher_dims None: a teacher-less trainer -- no teacher weights on the device, no teacher engine; every step
+        # then takes stored targets (`teacher_topk=`, topk_distill.TeacherTopK)
+        if (teacher_sd is None) != (teacher_dims is None):
+            raise ValueError("a teacher-less trainer is built with both teacher_sd and teacher_dims None")
+        self.sdims = WhisperDims.from_any(student_dims)
+        self.tdims = WhisperDims.from_any(teacher_dims) if teacher_dims is not None else None
         frozen = []
         if freeze_encoder:
             frozen.append("model.encoder.")
         if freeze_embed_positions:
             frozen.append("model.decoder.embed_positions.")
         self.student_store = ParamStore(ops, self.sdims, student_sd, trainable=True, frozen_prefixes=tuple(frozen))
-        self.teacher_store = ParamStore(ops, self.tdims, teacher_sd, trainable=False, round_bf16=True)
         self.student = WhisperEngine(ops, self.student_store, torch.float32)
-        self.teacher = WhisperEngine(ops, self.teacher_store, ops.lowp)
-        self.teacher.pad_gemm_rows = bool(pad_teacher_rows)   # decoder GEMMs of the frozen teacher over M padded to 320 rows
+        self.teacher_store = self.teacher = None
+        if teacher_sd is not None:
+            self.teacher_store = ParamStore(ops, self.tdims, teacher_sd, trainable=False, round_bf16=True)
+            self.teacher = WhisperEngine(ops, self.teacher_store, ops.lowp)
+            self.teacher.pad_gemm_rows = bool(pad_teacher_rows)   # decoder GEMMs of the frozen teacher over M padded to 320 rows
         # `dropout` / `activation_dropout` of the student's training forward (defaults: the student config's fields; the teacher,
         # eval_step and a frozen encoder's forward-only pass never drop).  Every rank draws its own masks, as each rank's torch
         # generator does in the reference: the effective seed is dropout_seed + rank.
@@ -331,12 +340,54 @@ class DistillationTrainer:
             return None
         return LiveRows.build(lens, Te, device)
 
+    def _check_targets(self, teacher_topk, labels, temperature, training):
+        """The argument rules of `teacher_topk=`, before anything is launched."""
+        if teacher_topk is None:
+            if self.teacher is None:
+                raise ValueError("this trainer was built without a teacher: every step takes stored targets (teacher_topk=)")
+            return
+        if not isinstance(teacher_topk, TeacherTopK):
+            raise ValueError("teacher_topk is a distil_whisper_amd.TeacherTopK")
+        teacher_topk.check(labels.shape, temperature, self.sdims.vocab)
+        if teacher_topk.idx.device != labels.device:
+            raise ValueError(f"teacher_topk lives on {teacher_topk.idx.device}, the labels on {labels.device}: move it with .to(device)")
+        if training and self.spec_augment is not None and self.augment_teacher:
+            raise ValueError("stored teacher targets saw the clean features: with SpecAugment active they need augment_teacher=False")
+
+    def teacher_targets(self, input_features, decoder_input_ids, labels, k=32, valid_len=None):
+        """Stored targets (TeacherTopK) of this batch from the trainer's own teacher at the trainer's temperature: the teacher
+        forward of `forward_backward` (with share_encoder: the student's encoder output and decoder inputs rebuilt from the labels),
+        then one `logits_topk` over its logits.  With `valid_len` only the live positions are computed; the others stay zero and are
+        never read (their labels are -100)."""
+        topk_distill.check_k(k, self.sdims.vocab)
+        if self.teacher is None:
+            raise ValueError("this trainer was built without a teacher")
+        ops, S, T = self.ops, self.student, self.teacher
+        B, Tfull = decoder_input_ids.shape
+        ids, lab, lens = trim_dead_positions(decoder_input_ids, labels, valid_len)
+        Td = ids.shape[1]
+        live = self._live_rows(lens, B, Td, ids.device)
+        feats = input_features.to(torch.float32).contiguous()
+        if self.share_encoder:
+            enc, _ = S.encode(feats, save=False)
+            ids = shift_tokens_right(lab, self.tdims.pad_token_id, self.tdims.decoder_start_token_id)
+        else:
+            enc, _ = T.encode(feats, save=False)
+        logits_t, _ = T.decode(ids.contiguous(), enc, save=False, live=live)
+        R = B * Td if live is None else live.n
+        idx, logp, rest = topk_distill.logits_topk(ops, logits_t[:R], self.sdims.vocab, self.temperature, k)
+        idx, logp, rest = topk_distill.scatter_targets(idx, logp, rest, B, Tfull, None if live is None else live.idx, Td)
+        return TeacherTopK(idx, logp, rest, self.temperature, self.sdims.vocab)
+
     def forward_backward(self, input_features, decoder_input_ids, labels, zero_grad=True, sync_grads=True, valid_len=None,
-                         _live=None):
+                         _live=None, teacher_topk=None):
         """One micro-batch: returns losses fp32[4] = (ce, kl, loss, n_valid) on the device (no host sync).
         zero_grad=False accumulates onto the gradients already in the flat buffer and sync_grads=False skips the
         all-reduce (gradient accumulation, `accelerator.accumulate` / DDP no_sync of run_distillation.py:1607).
-        `valid_len`: see trim_dead_positions."""
+        `valid_len`: see trim_dead_positions.
+        `teacher_topk` (TeacherTopK made at this trainer's temperature, covering the labels' [B, T]): the teacher forward does not
+        run; the targets are trimmed and index-selected like the labels and the loss is `distill_loss_topk`."""
+        self._check_targets(teacher_topk, labels, self.temperature, True)
         ops, S, T = self.ops, self.student, self.teacher
         decoder_input_ids, labels, lens = trim_dead_positions(decoder_input_ids, labels, valid_len)
         B, Td = decoder_input_ids.shape
@@ -359,7 +410,7 @@ class DistillationTrainer:
             feats_s = S.spec_augment(input_features, out=self._aug_buf)
             if self.augment_teacher:
                 feats_t = feats_s
-        side = self._tstream if (self.overlap_teacher and not self.share_encoder) else None
+        side = self._tstream if (self.overlap_teacher and not self.share_encoder and teacher_topk is None) else None
         if side is not None:
             main = torch.cuda.current_stream(input_features.device)
             side.wait_stream(main)
@@ -378,19 +429,24 @@ class DistillationTrainer:
             logits_s, dctx = S.decode(decoder_input_ids, enc_s, save=True, live=live)
         finally:
             S.training = False
-        if side is not None:
-            main.wait_stream(side)
-        elif self.share_encoder:
-            t_ids = shift_tokens_right(labels, self.tdims.pad_token_id, self.tdims.decoder_start_token_id)
-            logits_t, _ = T.decode(t_ids, enc_s, save=False, live=live)
-        else:
-            enc_t, _ = T.encode(feats_t, save=False)
-            logits_t, _ = T.decode(decoder_input_ids, enc_t, save=False, live=live)
-            del enc_t
         R = B * Td if live is None else live.n
-        losses = ops.distill_loss(logits_s[:R], logits_t[:R], labels_flat, self.sdims.vocab, self.temperature, 0.8,
-                                  self.kl_weight, 1.0, True)
-        del logits_t
+        if teacher_topk is not None:
+            idx, logp, rest = teacher_topk.trimmed(Td).rows(None if live is None else live.idx)
+            losses = topk_distill.distill_loss_topk(ops, logits_s[:R], idx, logp, rest, labels_flat, self.sdims.vocab,
+                                                    self.temperature, 0.8, self.kl_weight, 1.0, True)
+        else:
+            if side is not None:
+                main.wait_stream(side)
+            elif self.share_encoder:
+                t_ids = shift_tokens_right(labels, self.tdims.pad_token_id, self.tdims.decoder_start_token_id)
+                logits_t, _ = T.decode(t_ids, enc_s, save=False, live=live)
+            else:
+                enc_t, _ = T.encode(feats_t, save=False)
+                logits_t, _ = T.decode(decoder_input_ids, enc_t, save=False, live=live)
+                del enc_t
+            losses = ops.distill_loss(logits_s[:R], logits_t[:R], labels_flat, self.sdims.vocab, self.temperature, 0.8,
+                                      self.kl_weight, 1.0, True)
+            del logits_t
         self._gate = losses[3:4] if (zero_grad or self._gate is None) else self._gate + losses[3:4]
         if zero_grad:
             S.zero_small_grads(skip_weights=self.overwrite_wgrad)
@@ -409,11 +465,12 @@ class DistillationTrainer:
         S.join_wgrad_stream()
         return losses
 
-    def eval_step(self, input_features, decoder_input_ids, labels, valid_len=None):
+    def eval_step(self, input_features, decoder_input_ids, labels, valid_len=None, teacher_topk=None):
         """Forward-only CE + KL of the reference's `eval_step` (run_distillation.py:1498-1522: both models in eval
         mode under no_grad, the same loss mix, "temperature is always 1 for eval"): no activation is kept, nothing is
         written to the gradient buffer, the student logits are left intact.  Returns losses fp32[4] = (ce, kl, loss,
-        n_valid) on the device."""
+        n_valid) on the device.  `teacher_topk`: stored targets made at temperature 1.0 in place of the teacher forward."""
+        self._check_targets(teacher_topk, labels, 1.0, False)
         ops, S, T = self.ops, self.student, self.teacher
         decoder_input_ids, labels, lens = trim_dead_positions(decoder_input_ids, labels, valid_len)
         B, Td = decoder_input_ids.shape
@@ -422,16 +479,20 @@ class DistillationTrainer:
         decoder_input_ids = decoder_input_ids.contiguous()
         enc_s, _ = S.encode(input_features, save=False)
         logits_s, _ = S.decode(decoder_input_ids, enc_s, save=False, live=live)
+        R = B * Td if live is None else live.n
+        labels_flat = labels.reshape(-1).contiguous()
+        if live is not None:
+            labels_flat = labels_flat.index_select(0, live.idx)
+        if teacher_topk is not None:
+            idx, logp, rest = teacher_topk.trimmed(Td).rows(None if live is None else live.idx)
+            return topk_distill.distill_loss_topk(ops, logits_s[:R], idx, logp, rest, labels_flat, self.sdims.vocab,
+                                                  1.0, 0.8, self.kl_weight, 1.0, False)
         if self.share_encoder:
             t_ids = shift_tokens_right(labels, self.tdims.pad_token_id, self.tdims.decoder_start_token_id)
             logits_t, _ = T.decode(t_ids, enc_s, save=False, live=live)
         else:
             enc_t, _ = T.encode(input_features, save=False)
             logits_t, _ = T.decode(decoder_input_ids, enc_t, save=False, live=live)
-        R = B * Td if live is None else live.n
-        labels_flat = labels.reshape(-1).contiguous()
-        if live is not None:
-            labels_flat = labels_flat.index_select(0, live.idx)
         return ops.distill_loss(logits_s[:R], logits_t[:R], labels_flat, self.sdims.vocab,
                                 1.0, 0.8, self.kl_weight, 1.0, False)
 
@@ -480,13 +541,13 @@ class DistillationTrainer:
             st.repack_conv()
         self._gate = None
 
-    def train_step(self, input_features, decoder_input_ids, labels, lr=None, valid_len=None):
-        losses = self.forward_backward(input_features, decoder_input_ids, labels, valid_len=valid_len)
+    def train_step(self, input_features, decoder_input_ids, labels, lr=None, valid_len=None, teacher_topk=None):
+        losses = self.forward_backward(input_features, decoder_input_ids, labels, valid_len=valid_len, teacher_topk=teacher_topk)
         self.optimizer_step(lr)
         return losses
 
     # ---- the whole step as ONE captured HIP graph --------------------------------------------------------------
-    def train_step_graphed(self, inputs, decoder_input_ids, labels, lr=None, eager_steps=2, valid_len=None):
+    def train_step_graphed(self, inputs, decoder_input_ids, labels, lr=None, eager_steps=2, valid_len=None, teacher_topk=None):
         """`train_step` (preceded by the log-mel front end when `inputs` are waveforms [B, n_samples] instead of
         features [B, n_mels, 3000]) replayed from one HIP graph.  The shapes of a step are static, so its ~2 700
         launches on three streams (main, frozen teacher, weight gradients), every buffer address and the cross-stream
@@ -499,7 +560,10 @@ class DistillationTrainer:
         `valid_len` (trim_dead_positions) is part of the plan: one graph per (live decoder positions, packed rows), at most
         `max_graphs` of them, all replaying out of the SAME pool (they never run concurrently) and the same static input
         buffers.  Data-parallel runs keep the eager path (`train_step`): the bucketed RCCL all-reduce is issued between
-        the backward's layers from the host."""
+        the backward's layers from the host.  Stored teacher targets (`teacher_topk`) are not planned into a graph."""
+        if teacher_topk is not None:
+            raise NotImplementedError("train_step_graphed with stored teacher targets: use train_step(teacher_topk=...)")
+        self._check_targets(None, labels, self.temperature, True)
         if self.reducer is not None and self.reducer.active:
             raise RuntimeError("train_step_graphed: data-parallel steps run eagerly (RCCL buckets are issued from the host)")
         dev = self.student_store.P.device
@@ -602,14 +666,20 @@ class DistillationTrainer:
     def train_step_accumulated(self, micro_batches, lr=None):
         """Gradient accumulation over a list of (input_features, decoder_input_ids, labels): gradients are summed in
         the flat buffer, all-reduced once (with the last micro-batch) and averaged over the micro-batches in the fused
-        AdamW, like accelerate's `accumulate` context (loss / gradient_accumulation_steps)."""
+        AdamW, like accelerate's `accumulate` context (loss / gradient_accumulation_steps).
+        A micro-batch may carry more: `valid_len` and / or a TeacherTopK (stored targets), in either order behind the labels."""
         n = len(micro_batches)
         out = []
         self._accum = n
         try:
-            for i, mb in enumerate(micro_batches):      # (input_features, decoder_input_ids, labels[, valid_len])
+            for i, mb in enumerate(micro_batches):      # (input_features, decoder_input_ids, labels[, valid_len][, TeacherTopK])
+                extra = list(mb[3:])
+                tt = [x for x in extra if isinstance(x, TeacherTopK)]
+                vl = [x for x in extra if not isinstance(x, TeacherTopK)]
+                if len(tt) > 1 or len(vl) > 1:
+                    raise ValueError("a micro-batch is (input_features, decoder_input_ids, labels[, valid_len][, teacher_topk])")
                 out.append(self.forward_backward(mb[0], mb[1], mb[2], zero_grad=(i == 0), sync_grads=(i == n - 1),
-                                                 valid_len=mb[3] if len(mb) > 3 else None))
+                                                 valid_len=vl[0] if vl else None, teacher_topk=tt[0] if tt else None))
             self.optimizer_step(lr)
         finally:
             self._accum = 1

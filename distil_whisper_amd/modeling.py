@@ -801,6 +801,44 @@ class WhisperForConditionalGeneration(nn.Module):
                                _logits_lowp=lowp, _model=self, _rows=sel, _lazy=state)
 
     @torch.no_grad()
+    def teacher_topk(self, input_features=None, *, labels=None, decoder_input_ids=None, k=32, temperature=2.0,
+                     encoder_outputs=None, valid_len=None):
+        """Stored top-k teacher targets (topk_distill.TeacherTopK, the format of include/dwamd.h) of a batch, from the model a
+        labelling job already holds: one teacher-forced pass without saved activations, then one `logits_topk` launch over its
+        logits.  Given `labels`, the decoder inputs are the labels shifted right, as the trainer builds them; `valid_len` (one int
+        or one per sequence, distill.trim_dead_positions) leaves the dead positions out -- they stay zero in the result and are
+        never read.  A trainer uses the result as `teacher_topk=` at the same temperature."""
+        from . import topk_distill
+        from .distill import shift_tokens_right, trim_dead_positions
+        from .engine import LiveRows
+        d = self.dims
+        k = topk_distill.check_k(k, d.vocab)
+        if not float(temperature) > 0.0:
+            raise ValueError(f"temperature > 0, got {temperature!r}")
+        if decoder_input_ids is None:
+            if labels is None:
+                raise ValueError("decoder_input_ids or labels are required")
+            decoder_input_ids = shift_tokens_right(labels, d.pad_token_id, d.decoder_start_token_id)
+        if decoder_input_ids.shape[1] > d.max_tgt:
+            raise ValueError(f"the sequence length {decoder_input_ids.shape[1]} exceeds the model's {d.max_tgt} positions")
+        self._sync_shadow()
+        if encoder_outputs is not None:
+            enc, _ = self._given_encoder_output(encoder_outputs)
+        elif input_features is None:
+            raise ValueError("input_features or encoder_outputs are required")
+        else:
+            enc, _ = self.engine.encode(input_features.to(torch.float32).contiguous(), save=False)
+        B, T = decoder_input_ids.shape
+        ids, _, lens = trim_dead_positions(decoder_input_ids, decoder_input_ids, valid_len)
+        Td = ids.shape[1]
+        live = LiveRows.build(lens, Td, ids.device) if lens is not None and sum(lens) < B * Td else None
+        logits, _ = self.engine.decode(ids.contiguous(), enc, save=False, live=live)
+        R = B * Td if live is None else live.n
+        idx, logp, rest = topk_distill.logits_topk(self.ops, logits[:R], d.vocab, temperature, k)
+        idx, logp, rest = topk_distill.scatter_targets(idx, logp, rest, B, T, None if live is None else live.idx, Td)
+        return topk_distill.TeacherTopK(idx, logp, rest, float(temperature), d.vocab)
+
+    @torch.no_grad()
     def generate(self, input_features=None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  prefix_allowed_tokens_fn=None, synced_gpus=False, return_timestamps=None, task=None, language=None,
                  is_multilingual=None, prompt_ids=None, prompt_condition_type=None, condition_on_prev_tokens=None,

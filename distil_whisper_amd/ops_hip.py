@@ -105,6 +105,12 @@ _SIGS = {
                          C.c_void_p], C.c_int),
     "dw_distill_loss_w": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p,
                            C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "dw_logits_topk": ([C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                       C.c_int),
+    "dw_distill_loss_topk": ([C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64] + [C.c_float] * 4 +
+                             [C.c_void_p] * 6, C.c_int),
+    "dw_distill_loss_topk_w": ([C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_float] +
+                               [C.c_void_p] * 6, C.c_int),
     "dw_embed_fwd": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                       C.c_void_p], C.c_int),
     "dw_embed_bwd": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
@@ -686,6 +692,49 @@ class HipOps:
                                            self._stream()), "distill_loss")
         return (losses, row_ce, row_kl) if return_rows else losses
 
+    def logits_topk(self, logits, V, temperature, k):
+        """Stored top-k teacher targets of every row (include/dwamd.h): logits bf16 [rows, ld] -> idx int32 [rows, k],
+        logp f32 [rows, k], rest f32 [rows].  One launch."""
+        rows, ld = logits.shape
+        assert logits.dtype == torch.bfloat16 and logits.is_contiguous() and logits.device == self.device
+        idx = self.empty((rows, int(k)), torch.int32)
+        logp = self.empty((rows, int(k)), torch.float32)
+        rest = self.empty((rows,), torch.float32)
+        self._chk(self.lib.dw_logits_topk(_p(logits), rows, V, ld, float(temperature), int(k), _p(idx), _p(logp), _p(rest),
+                                          self._stream()), "logits_topk")
+        return idx, logp, rest
+
+    def distill_loss_topk(self, s_logits, idx, logp, rest, labels, V, temperature, ce_weight, kl_weight, grad_scale, want_grad,
+                          grad_out=None, weights_dev=None, return_rows=False):
+        """`distill_loss` with the teacher row replaced by its stored targets idx int32 / logp f32 [rows, k], rest f32 [rows] (made
+        at `temperature`): same returns, same `grad_out` / `weights_dev` / `return_rows`."""
+        rows, ld = s_logits.shape
+        if grad_out is not None:
+            assert want_grad and grad_out.shape == s_logits.shape and grad_out.dtype == torch.bfloat16 and grad_out.is_contiguous()
+        assert s_logits.dtype == torch.bfloat16 and s_logits.is_contiguous()
+        assert idx.dtype == torch.int32 and logp.dtype == torch.float32 and rest.dtype == torch.float32
+        assert idx.dim() == 2 and idx.shape[0] == rows and logp.shape == idx.shape and rest.numel() == rows
+        assert idx.is_contiguous() and logp.is_contiguous() and rest.is_contiguous()
+        assert s_logits.device == idx.device == logp.device == rest.device == labels.device == self.device
+        assert labels.dtype == torch.int64 and labels.numel() == rows and labels.is_contiguous()
+        k = idx.shape[1]
+        losses = self.empty((4,), torch.float32)
+        row_ce = self.empty((rows,), torch.float32)
+        row_kl = self.empty((rows,), torch.float32)
+        counts = self.empty((2,), torch.int32)
+        dl = (_p(s_logits) if grad_out is None else _p(grad_out)) if want_grad else None
+        if weights_dev is not None:
+            assert weights_dev.dtype == torch.float32 and weights_dev.numel() == 2 and weights_dev.is_contiguous()
+            self._chk(self.lib.dw_distill_loss_topk_w(_p(s_logits), _p(idx), _p(logp), _p(rest), k, _p(labels), rows, V, ld,
+                                                      float(temperature), _p(weights_dev), float(grad_scale), _p(losses), dl,
+                                                      _p(row_ce), _p(row_kl), _p(counts), self._stream()), "distill_loss_topk_w")
+        else:
+            self._chk(self.lib.dw_distill_loss_topk(_p(s_logits), _p(idx), _p(logp), _p(rest), k, _p(labels), rows, V, ld,
+                                                    float(temperature), float(ce_weight), float(kl_weight), float(grad_scale),
+                                                    _p(losses), dl, _p(row_ce), _p(row_kl), _p(counts), self._stream()),
+                      "distill_loss_topk")
+        return (losses, row_ce, row_kl) if return_rows else losses
+
     def embed_fwd(self, ids, tok, pos, out_dtype, rows_alloc=0, out=None):
         """rows_alloc > B*T: the output buffer gets that many rows (the extra rows are zero; callers whose GEMMs run
         over a padded row count).  out: a contiguous [max(rows_alloc, B*T), D] buffer of out_dtype to fill instead of a new one."""
@@ -1176,7 +1225,7 @@ def _timed(key):
     return deco
 
 
-for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("distill_loss", "loss"),
+for _name, _key in (("layernorm_fwd", "ln_fwd"), ("layernorm_bwd", "ln_bwd"), ("distill_loss", "loss"), ("distill_loss_topk", "loss"), ("logits_topk", "topk"),
                     ("logmel", "logmel"), ("adamw", "adamw"), ("adamw_dev", "adamw"), ("cast_bf16", "cast"), ("colsum", "colsum"),
                     ("sumsq", "sumsq"), ("embed_fwd", "embed"), ("embed_bwd", "embed"), ("im2col_mel", "conv_aux"),
                     ("im2col_s2", "conv_aux"), ("col2im_s2_gelu_bwd", "conv_aux"), ("gelu_bwd", "conv_aux"),

@@ -212,6 +212,51 @@ int dw_distill_loss_w(const void* s_logits, const void* t_logits, const int64_t*
                       float temperature, const float* weights, float grad_scale, float* losses, void* dlogits,
                       float* row_ce, float* row_kl, int32_t* counts, void* stream);
 
+/* ---- Stored top-k teacher targets (offline distillation; the format is stated here and nowhere else) -------------------------
+ * For one label position -- one row z of teacher logits, bf16, V valid columns --, a temperature T > 0 and 1 <= k <= 64, k < V:
+ *   K        the k columns with the largest z; equal values go to the LOWER column (-0 counts as +0); stored in order of value
+ *            descending, then column ascending.  bf16 widens exactly: the selection is exact and has one right answer
+ *   logp[j]  = z[K_j] / T - logsumexp(z / T) over all V columns, fp32
+ *   rest     = sum over c not in K of exp(z[c] / T - lse), fp32: summed over the tail term by term, never 1 - sum exp(logp);
+ *              exactly 0 when every tail term underflows.  (Computed as sum_{c not in K} e_c / sum_c e_c, e_c = exp((z[c] - max z) / T),
+ *              and logp[j] as (z[K_j] - max z) / T - log sum_c e_c: the same numbers without a rounded lse inside an exponent.)
+ * A batch: idx int32 [B, Td, k], logp float32 [B, Td, k], rest float32 [B, Td], with the temperature and V they were made at;
+ * targets are bound to that temperature.
+ *
+ * dw_logits_topk: logits bf16 [rows][ld] -> idx [rows][k], logp [rows][k], rest [rows].  One launch, one workgroup per row; no
+ * floating-point atomics: equal inputs give equal bits.  Checked before the launch, in this order:
+ *   DW_EINVAL  a null pointer; logits not 8-byte, idx / logp / rest not 4-byte aligned; rows < 1, V < 1, ld < V, ld not a multiple
+ *              of 4, temperature not in (0, FLT_MAX]; k < 1 or k >= V
+ *   DW_EUNSUP  V > 53 248 (thirteen 4-column chunks per lane), k > 64
+ * A refused call launches nothing and writes nothing. */
+int dw_logits_topk(const void* logits, int rows, int V, int64_t ld, float temperature, int k, int32_t* idx, float* logp,
+                   float* rest, void* stream);
+/* dw_distill_loss with the teacher row replaced by its stored targets (idx / logp int32 / f32 [rows][k], rest f32 [rows], made at
+ * `temperature`): the KL divergence of the two distributions with the columns outside K merged into one bucket.  It never exceeds
+ * the dense KL and equals it, gradient included, when rest == 0.  Per row, q = softmax(z_s / T), p_j = exp(logp[j]), r = rest:
+ *   ce      the dense kernel's term, counted where label != -100
+ *   row_kl  = sum_j p_j (logp[j] - log q_{K_j}) + r (log r - log qR)     (second term 0 when r == 0; counted where label >= 0;
+ *             stored like the dense kernel's row_kl: T^2 enters with the mean, losses[1] = sum(row_kl) / n * T^2)
+ *   qR      = sum over c not in K of q_c, accumulated over the non-members themselves (a membership bitmap of V bits in LDS), never
+ *             "whole minus the members".  With e_c = exp((z_c - max z) / T): qR = max(sum_{c not in K} e_c, FLT_MIN) / sum_c e_c --
+ *             the tail sum is clamped from below by FLT_MIN = 2^-126, so a row whose student tail underflows stays finite
+ *   the KL part of the gradient, in the place of softmax(z_s/T) - softmax(z_t/T): q_c - p_c for c in K, q_c (1 - r / qR) otherwise
+ * losses, dlogits (may alias s_logits; columns V..ld-1 zeroed), row_ce / row_kl / counts, grad_scale and the all-ignored batch (NaN
+ * means, a zero gradient, losses[3] = 0) are dw_distill_loss's.  A row whose label excludes it from both sums (-100, or any other
+ * negative label) is not looked at: whatever idx / logp / rest hold there changes nothing and is not dereferenced.  In a counted
+ * row the k indices are distinct columns of [0, V) (the caller's promise; an index outside that range is skipped).
+ * Checked before any launch: DW_EINVAL as dw_distill_loss (s_logits / dlogits 16-byte aligned, ld a multiple of 8), a null or not
+ * 4-byte aligned idx / logp / rest, k < 1 or k >= V; then DW_EUNSUP for V > 53 248 or k > 64.  Nothing is written then. */
+int dw_distill_loss_topk(const void* s_logits, const int32_t* idx, const float* logp, const float* rest, int k,
+                         const int64_t* labels, int rows, int V, int64_t ld, float temperature, float ce_weight, float kl_weight,
+                         float grad_scale, float* losses, void* dlogits, float* row_ce, float* row_kl, int32_t* counts,
+                         void* stream);
+/* The same with the mix read from device memory, as dw_distill_loss_w. */
+int dw_distill_loss_topk_w(const void* s_logits, const int32_t* idx, const float* logp, const float* rest, int k,
+                           const int64_t* labels, int rows, int V, int64_t ld, float temperature, const float* weights,
+                           float grad_scale, float* losses, void* dlogits, float* row_ce, float* row_kl, int32_t* counts,
+                           void* stream);
+
 /* ---- embeddings (TF:modeling_whisper.py:675-676, 736-762) ------------------------------------------------------
  * out[b*T+t][:] = tok[ids[b*T+t]][:] + pos[t][:]; tables f32 or bf16 (tab_dtype); out f32 or bf16.
  * D a multiple of 4; tok, pos and out aligned to four of their elements (8 bytes for bf16, 16 for f32), DW_EINVAL otherwise.
